@@ -7,9 +7,16 @@ inputs resident in HBM before the timed region.  The batch axis shards across GP
 (forward-only replicas, weak scaling: 256 rows per GPU); the only collectives are the timing barrier and the
 max-over-ranks of the elapsed time.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--precision fp32|bf16x3|f16f6|bf16] [--batch B] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--precision fp32|bf16x3|f16f6|bf16] [--batch B] [--dump-outputs DIR]
+    python bench.py --full [--no-cpu-baseline] [--no-fp32-exact] [--no-subrecords]
+                                              the headline line plus its sub-records: exact-fp32 / bf16x3 legs and their checks of the timed
+                                              launch, stand-alone a-side kernels, c3 / c4 forwards, projection GEMM, CPU baseline + oracle parity
     python bench.py --config c3|c4            full-model forwards of BASELINE configs[2] / [3] (bf16), their own flop tally and roofline
     python bench.py --mode train              data-parallel training step (configs[4] shape) of the CTI fusion block
+
+A plain run (no --full) sets up, warms up, times the K steps and prints the headline line; the roofline / kernel_ms / guard fields come from
+hipEvents inside those K steps.  --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float32, at most 64 MB in all;
+the inputs are seeded, so two builds run with the same arguments can be compared array by array).
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment starts the N ranks itself (a `torch.distributed.run` child, spawned before
 anything touches a GPU) and relays rank 0's JSON line; under `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N` it
@@ -39,6 +46,38 @@ HBM_PEAK_GBS = 8000.0
 SEED = 1204                                                         # the reference's default seed (src/FFOE/main.py:53)
 DTYPE_NAME = {"fp32": "f32", "bf16x3": "f32 (bf16x3 split products, f32 accumulate)", "bf16": "bf16 products, f32 accumulate",
               "f16f6": "f32 (f16 product + two block-scaled fp6 correction products, f32 accumulate)"}
+DUMP_LIMIT = 64 << 20                                               # --dump-outputs: bytes written, all arrays together
+DUMP_SAMPLE = 1 << 22                                               # elements of the seeded sample of an output too large to write whole
+
+
+def forward_dump(out, limit=DUMP_LIMIT, sample=DUMP_SAMPLE):
+    """--dump-outputs of the configs[1] forward.  Its output (B x V x Q x A x glimpse fp32: 3.2 GB at B = 256) is written whole when it fits
+    `limit`; otherwise the first and the last sample whole and `sample` elements of the flattened tensor at positions drawn from
+    np.random.RandomState(SEED) (sorted; the same positions on every run with the same shape)."""
+    if out.numel() * 4 <= limit:
+        return {"tcnet_out": out}
+    flat = out.reshape(-1)
+    idx = np.sort(np.random.RandomState(SEED).randint(0, flat.numel(), size=sample, dtype=np.int64))
+    return {"tcnet_out_first_sample": out[0], "tcnet_out_last_sample": out[-1],
+            "tcnet_out_sampled": flat[torch.from_numpy(idx).to(out.device)]}
+
+
+def write_outputs(dirname, arrays, limit=DUMP_LIMIT):
+    """DIR/<name>.npy for every array: float64 stays float64, every other dtype is widened / converted to float32.  Refuses to write more than
+    `limit` bytes in all.  Returns the bytes written."""
+    host = {}
+    for name, t in arrays.items():
+        t = t.detach().cpu()
+        host[name] = np.ascontiguousarray((t if t.dtype == torch.float64 else t.float()).numpy())
+    total = sum(a.nbytes for a in host.values())
+    if total > limit:
+        raise SystemExit("bench.py: --dump-outputs would write %d bytes (limit %d)" % (total, limit))
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    print("bench.py: wrote %s (%.1f MB) to %s" % (", ".join("%s%s" % (n, list(a.shape)) for n, a in host.items()), total / 2**20, dirname),
+          file=sys.stderr, flush=True)
+    return total
 
 
 def flops_per_sample(c):
@@ -439,9 +478,10 @@ def model_setup(config, B, rank, dev):
                               "the two models on sibling streams (ops.run_concurrently; CTI_BENCH_SERIAL_MODELS=1 = one after the other)")))
 
 
-def model_measure(setup, steps, warmup, world, dist, dev, graphed, prec):
+def model_measure(setup, steps, warmup, world, dist, dev, graphed, prec, dump=None):
     """Times setup['fwd'] (hipGraph replay unless graphed is False) and checks the forward that was TIMED (the replayed graph's static output)
-    against the oracle on its first 4 rows.  Returns (elapsed, parity record)."""
+    against the oracle on its first 4 rows.  `dump(out)`, if given, is called with the timed forward's output before the checks.
+    Returns (elapsed, parity record)."""
     from oracle.cti_oracle import norm_max_err
     holder = {}
 
@@ -467,6 +507,8 @@ def model_measure(setup, steps, warmup, world, dist, dev, graphed, prec):
         else:
             el = measure(step, steps, warmup, world, torch.cuda.synchronize, dist, dev)
     out = holder["out"]
+    if dump is not None:
+        dump(out)
     out0 = out[0] if isinstance(out, tuple) else out
     assert tuple(out0.shape) == setup["out_shape"] and bool(torch.isfinite(out0).all())
     parity = {"rows": 4, "tol": MODEL_TOL[prec], "vs": "oracle/cti_models.py (numpy fp32) on the first 4 rows of the timed forward's output"}
@@ -501,7 +543,11 @@ def run_model(args, world, rank, dev, dist):
     B = args.batch
     setup = model_setup(args.config, B, rank, dev)
     graphed = not args.no_graph
-    el, parity = model_measure(setup, args.steps, args.warmup, world, dist, dev, graphed, prec)
+    dump = None
+    if args.dump_outputs and rank == 0:
+        names = {"c3": ("mc_cti_logits",), "c4": ("ban_logits", "cti_logits")}[args.config]
+        dump = lambda out: write_outputs(args.dump_outputs, dict(zip(names, out if isinstance(out, tuple) else (out,))))    # noqa: E731
+    el, parity = model_measure(setup, args.steps, args.warmup, world, dist, dev, graphed, prec, dump)
     flops, workload = setup["flops"], setup["workload"]
     dinfo = dist_info(dist, world, rank, dev)
     if dist.is_initialized():
@@ -678,8 +724,10 @@ def run_forward(args, world, rank, dev, dist):
         kt = cti_amd.ops.profile_stop()
     out = res_holder["out"]
     assert out.shape == (c["B"], c["V"], c["Q"], c["A"], c["glimpse"])
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, forward_dump(out))
     fp32_exact = None
-    if rank == 0 and world == 1 and args.precision != "fp32" and not args.no_fp32_exact:
+    if args.full and rank == 0 and world == 1 and args.precision != "fp32" and not args.no_fp32_exact:
         # the strict-fp32 arithmetic (v_mfma_f32_32x32x2_f32, bitwise an fmaf chain) on the driver's clock, a few steps
         gpu_first = out[:4].cpu().numpy()
         timed_out = out                                       # kept until the bf16x3 leg below has looked at every sample of it (3.2 GB of the 288)
@@ -729,7 +777,7 @@ def run_forward(args, world, rank, dev, dist):
         res_holder.pop("out", None)
     else:
         bf16x3 = None
-        gpu_first = out[:4].cpu().numpy() if rank == 0 else None
+        gpu_first = out[:4].cpu().numpy() if rank == 0 and args.full else None
     res = None
     if rank == 0:
         fl = flops_per_sample(c)
@@ -782,7 +830,7 @@ def run_forward(args, world, rank, dev, dist):
             res["roofline"]["l2_to_lds_note"] = "derived: tiles x (256 + 192) operand rows x K x 2.8125 B per launch; l2_hit_rate / mfma_busy_frac: PMC passes named in traffic_source"
         rk = [{"kernel": "gemm_f16f6_kernel<EPI_INTERLEAVE2> mode-3 product + rank sum" if args.precision == "f16f6" else "mode-3 product + rank sum: " + variant,
                "ms": core_ms, "bound": "mfma", "achieved": achieved, "unit": "TFLOP/s", "frac": achieved / peak, "flops": core_flops}]
-        if args.precision == "f16f6" and world == 1 and not args.no_subrecords:
+        if args.full and args.precision == "f16f6" and world == 1 and not args.no_subrecords:
             out = None
             res_holder.pop("out", None)
             torch.cuda.empty_cache()
@@ -801,12 +849,12 @@ def run_forward(args, world, rank, dev, dist):
             res["fp32_exact"] = fp32_exact
         if bf16x3 is not None:
             res["bf16x3"] = bf16x3
-        if world == 1 and not args.no_subrecords and args.batch == C2["B"]:
+        if args.full and world == 1 and not args.no_subrecords and args.batch == C2["B"]:
             # BASELINE configs[2] / [3] on the same clock: full-model forwards, bf16, hipGraph replay, each checked against the oracle
             torch.cuda.empty_cache()
             res["configs"] = {"c3": model_subrecord("c3", dev), "c4": model_subrecord("c4", dev)}
             res["projection_gemm"] = projection_gemm_record(dev)
-        if not args.no_cpu_baseline and world == 1:          # the CPU baseline is reported at N=1 only
+        if args.full and not args.no_cpu_baseline and world == 1:      # the CPU baseline is reported at N=1 only
             state = {k: t_.detach().cpu().numpy() for k, t_ in net.state_dict().items()}
             res["cpu_baseline"] = cpu_baseline(c, state, (v, q, a), gpu_first, args.cpu_budget)
     dinfo = dist_info(dist, world, rank, dev)
@@ -832,7 +880,7 @@ def main():
     ap.add_argument("--mode", default="forward", choices=["forward", "train"], help="forward (the BASELINE metric) or train (DP step)")
     ap.add_argument("--config", default="c2", choices=["c2", "c3", "c4"], help="c2 = BASELINE configs[1] (the metric); c3 / c4 = full-model forwards of configs[2] / [3]")
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200, help="timed steps (about 1 s of GPU time at the default workload: long enough for the clocks to settle; + ~20 s of CPU baseline)")
+    ap.add_argument("--steps", type=int, default=200, help="timed steps (about 1 s of GPU time at the default workload: long enough for the clocks to settle; --full adds ~20 s of CPU baseline)")
     ap.add_argument("--warmup", type=int, default=20, help="untimed steps: allocator growth, one-time kernel attributes, clock ramp")
     ap.add_argument("--batch", type=int, default=C2["B"], help="rows per GPU (default 256 = BASELINE configs[1])")
     ap.add_argument("--precision", default=None, choices=["fp32", "bf16x3", "bf16", "f16f6"],
@@ -841,12 +889,22 @@ def main():
                          "everywhere (1.5e-5); fp32: exact fp32 MFMA")
     ap.add_argument("--graph", action="store_true", help="--mode train with a process group: capture the whole step INCLUDING the all-reduce into one hipGraph (aborts on ROCm 7.0 / torch 2.10; the default there is two graphs around an eager all-reduce)")
     ap.add_argument("--no-graph", action="store_true", help="--mode train: eager launches even on one rank")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-fp32-exact", action="store_true", help="skip the 4-step exact-fp32 sub-record of the default line")
-    ap.add_argument("--no-subrecords", action="store_true", help="skip the c3 / c4 model sub-records and the stand-alone a-side kernel timings of the default line")
+    ap.add_argument("--full", action="store_true",
+                    help="the headline forward line with its sub-records (each after the timed steps): the exact-fp32 and bf16x3 legs and their every-sample checks "
+                         "of the timed launch, the stand-alone a-side kernel timings, the c3 / c4 model forwards, the projection GEMM and the CPU baseline with "
+                         "the oracle parity of the timed launch.  Off: the headline line only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline (and with it the oracle parity of the timed launch)")
+    ap.add_argument("--no-fp32-exact", action="store_true", help="--full: skip the 4-step exact-fp32 sub-record (and the bf16x3 one)")
+    ap.add_argument("--no-subrecords", action="store_true", help="--full: skip the c3 / c4 model sub-records and the stand-alone a-side kernel timings")
     ap.add_argument("--cpu-budget", type=float, default=20.0)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32, <= 64 MB in all; a seeded sample of a larger output)")
     ap.add_argument("--dry-launch", action="store_true", help="launch + rendezvous + timing path only (gloo on CPU, no GPU work)")
     args = ap.parse_args()
+    if args.dump_outputs and (args.mode == "train" or args.dry_launch):
+        ap.error("--dump-outputs: the forward workloads only (a training step returns nothing to its caller; --dry-launch computes nothing)")
+    if args.steps < 1:
+        ap.error("--steps: at least one timed step")
     args.precision_given = args.precision is not None
     if args.precision is None:
         args.precision = os.environ.get("CTI_PRECISION", "f16f6" if (args.mode == "forward" and args.config == "c2") else "bf16x3")

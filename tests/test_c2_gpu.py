@@ -280,3 +280,40 @@ def test_f16f6_forward_around_its_fast_paths(B, V, Q, A, vd, qd, ad, h, R):
     e3, e6 = O.norm_max_err(outs["bf16x3"], ref), O.norm_max_err(outs["f16f6"], ref)
     print("TCNet.forward B=%d V=%d Q=%d A=%d h=%d R=%d: bf16x3 %.3g, f16f6 %.3g vs float64" % (B, V, Q, A, h, R, e3, e6))
     assert e3 < TOL and e6 < TOL
+
+
+def test_plain_bench_run_dumps_its_last_timed_step(tmp_path):
+    """`bench.py --steps 2 --warmup 1 --dump-outputs DIR`, twice: the headline line only (no sub-records), exactly the steps asked for, and
+    the dumped arrays are the configs[1] output of the timed launch -- its first and last sample against the float64 oracle on the same
+    seeded inputs and parameters, and every array the same from run to run."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    import bench
+    lines, dumps = [], []
+    for k in range(2):
+        d = tmp_path / ("run%d" % k)
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--dump-outputs", str(d)],
+                           stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines.append(json.loads(r.stdout.strip().splitlines()[-1]))
+        dumps.append({f[:-4]: np.load(str(d / f)) for f in os.listdir(str(d))})
+    for res in lines:
+        assert res["steps"] == 2 and res["warmup"] == 1 and res["ms_per_step"] > 0 and res["value"] > 0 and res["unit"] == "samples/s"
+        assert res["higher_is_better"] is True and res["dtype"] == bench.DTYPE_NAME["f16f6"]
+        assert not {"cpu_baseline", "fp32_exact", "bf16x3", "configs", "projection_gemm"} & set(res)
+    assert sorted(dumps[0]) == ["tcnet_out_first_sample", "tcnet_out_last_sample", "tcnet_out_sampled"]
+    assert sum(a.nbytes for a in dumps[0].values()) <= bench.DUMP_LIMIT and all(a.dtype == np.float32 for a in dumps[0].values())
+    for name in dumps[0]:
+        assert dumps[0][name].shape == dumps[1][name].shape and O.norm_max_err(dumps[1][name], dumps[0][name]) < 1e-6, name
+    c = bench.C2
+    torch.manual_seed(bench.SEED)
+    net = cti_amd.TCNet(c["v_dim"], c["q_dim"], c["a_dim"], c["h_mm"], 1, c["rank"], c["glimpse"])
+    params = {k: t.detach().numpy() for k, t in net.state_dict().items()}
+    v, q, a = (t.numpy() for t in bench.synth_inputs(c, c["B"], bench.SEED + 1, "cpu"))
+    for b, name in ((0, "tcnet_out_first_sample"), (c["B"] - 1, "tcnet_out_last_sample")):
+        ref = O.tcnet_forward(v[b:b + 1], q[b:b + 1], a[b:b + 1], params, dtype=np.float64)[0]
+        assert O.norm_max_err(dumps[0][name], ref) < TOL, name

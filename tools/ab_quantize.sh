@@ -1,4 +1,4 @@
-run() { python bench.py --steps 60 --warmup 15 --no-cpu-baseline --no-fp32-exact 2>/dev/null | tail -1 | python -c "
+run() { python bench.py --full --steps 60 --warmup 15 --no-cpu-baseline --no-fp32-exact 2>/dev/null | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 ks={r['kernel'][:28]: round(r['ms'],3) for r in d['roofline_kernels']['kernels']}

@@ -5,9 +5,9 @@ set -u
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 E=gpurun_out/evidence; rm -rf $E; mkdir -p $E
 python -m pytest tests -m gpu -q > $E/pytest_gpu.log 2>&1; tail -2 $E/pytest_gpu.log
-python bench.py > $E/bench_f16f6.log 2>&1; tail -1 $E/bench_f16f6.log | cut -c1-200
-python bench.py --precision bf16x3 --no-cpu-baseline --no-subrecords > $E/bench_bf16x3.log 2>&1
-python bench.py --precision fp32 --no-cpu-baseline --no-subrecords > $E/bench_fp32.log 2>&1
+python bench.py --full > $E/bench_f16f6.log 2>&1; tail -1 $E/bench_f16f6.log | cut -c1-200
+python bench.py --full --precision bf16x3 --no-cpu-baseline --no-subrecords > $E/bench_bf16x3.log 2>&1
+python bench.py --full --precision fp32 --no-cpu-baseline --no-subrecords > $E/bench_fp32.log 2>&1
 python bench.py --precision bf16 --no-cpu-baseline --no-fp32-exact --no-subrecords > $E/bench_bf16.log 2>&1
 python bench.py --mode train > $E/bench_train.log 2>&1; tail -1 $E/bench_train.log | cut -c1-200
 CTI_BENCH_FORCE_DIST=1 python bench.py --mode train > $E/bench_train_rccl_world1.log 2>&1; tail -1 $E/bench_train_rccl_world1.log | cut -c1-200   # two graphs around an eager RCCL all-reduce
