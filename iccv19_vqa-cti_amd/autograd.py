@@ -33,6 +33,49 @@ class WNLinearFn(torch.autograd.Function):
         return dx, dV.view_as(V), dg.view_as(g), db, None, None, None
 
 
+class LinearFn(torch.autograd.Function):
+    """y = x @ W^T + b: a plain nn.Linear (no weight norm; the SAN layers, src/attention.py:78-88).  bias may be None.  dx_prec: the
+    precision of the input-gradient product (None = the package's mode)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, dx_prec=None):
+        y = ops.wn_linear(x, weight, None, weight.shape[0], bias, False)
+        ctx.save_for_backward(x, weight)
+        ctx.has_bias = bias is not None
+        ctx.dx_prec = dx_prec
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, W = ctx.saved_tensors
+        N, K = W.shape
+        dy2 = dy.contiguous().view(-1, N)
+        dx = ops.gemm_nn(dy2, W.contiguous(), prec=ctx.dx_prec).view(x.shape) if ctx.needs_input_grad[0] else None
+        dW = ops.gemm_tn(dy2, x.contiguous().view(-1, K)) if ctx.needs_input_grad[1] else None
+        db = ops.col_sum(dy2) if ctx.has_bias and ctx.needs_input_grad[2] else None
+        return dx, dW, db, None
+
+
+class SanAttendFn(torch.autograd.Function):
+    """pooled = sum_n softmax_n(w . drop(tanh(qv + P_n)) + b, masked) X_n: one attention step of StackedAttention (src/attention.py:96-116,
+    130-144) as cti_san_attend_fwd / _bwd.  X None: the pool source is P itself (the stacks after the first).  keep: None or the uint8 (B, N, A)
+    keep-mask of the dropout on h (p_drop)."""
+
+    @staticmethod
+    def forward(ctx, P, qv, w, b, X, keep, p_drop, v_mask):
+        pooled, prob, _ = ops.san_attend(P, qv, w, b, X=X, keep=keep, p_drop=p_drop, v_mask=v_mask)
+        ctx.save_for_backward(P, qv, w, prob, X, keep)
+        ctx.p_drop = p_drop
+        return pooled
+
+    @staticmethod
+    def backward(ctx, dpooled):
+        P, qv, w, prob, X, keep = ctx.saved_tensors
+        need_dX = X is not None and ctx.needs_input_grad[4]
+        dP, dqv, dw, db, dX = ops.san_attend_bwd(dpooled, P, qv, w, prob, X=X, keep=keep, p_drop=ctx.p_drop, need_dX=need_dX)
+        return dP, dqv, dw.view(w.shape), db if ctx.needs_input_grad[3] else None, dX, None, None, None
+
+
 class DropoutFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, p):

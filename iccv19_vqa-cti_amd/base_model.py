@@ -7,7 +7,8 @@ Everything between the token ids and the logits runs in the HIP library: embeddi
 residual projections (`q_prj(b_emb.unsqueeze(1)) + q_emb` = one GEMM + one broadcast-add kernel, no (B,1,H) round trip
 through a generic broadcast), the sequence sums and the classifier.
 
-Outside the path (they raise): the counting module (`--use_counter`, src/counting.py) and the SAN baseline; tf-idf
+The SAN baseline (src/FFOE/base_model.py:70-93,162-174; src/MC/base_model.py:79-108,211-230) is StackedAttentionModel /
+MCStackedAttentionModel with build_san / build_mc_san.  Outside the path (it raises): the counting module (`--use_counter`, src/counting.py); tf-idf
 initialisation of the embeddings (`tfidf_loading`, src/utils.py) is data preparation -- load a checkpoint or call
 `WordEmbedding.init_embedding`."""
 import contextlib
@@ -20,7 +21,7 @@ import torch.nn as nn
 
 from . import autograd as AG
 from . import ops
-from .attention import BiAttention, TriAttention
+from .attention import BiAttention, StackedAttention, TriAttention
 from .bc import BCNet
 from .classifier import SimpleClassifier
 from .fc import BatchedLinears, FCNet, HoistedProjection, WNLinear
@@ -720,3 +721,78 @@ def build_mc_ban(args, dataset):
         _no_counter(True)
     return MCBanModel(dataset, w_emb, q_emb, wa_emb, ans_emb, v_att, b_net, va_att, tva_net, q_prj, a_prj, c_prj, classifier, None,
                       args.op, args.gamma)
+
+
+class StackedAttentionModel(nn.Module):
+    """FFOE SAN (src/FFOE/base_model.py:70-93): question GRU -> StackedAttention -> classifier; forward(v, q) returns the logits."""
+
+    def __init__(self, w_emb, q_emb, v_att, classifier):
+        super(StackedAttentionModel, self).__init__()
+        self.w_emb = w_emb
+        self.q_emb = q_emb
+        self.v_att = v_att
+        self.classifier = classifier
+
+    def forward(self, v, q):
+        v = _v_as_taken(v, self)
+        q_emb = self.q_emb.forward_all(self.w_emb.rows16(q))[:, -1]          # [batch, q_dim]: the last hidden state (QuestionEmbedding.forward)
+        att = self.v_att(v, q_emb)
+        return self.classifier(att)
+
+
+class MCStackedAttentionModel(nn.Module):
+    """MC SAN (src/MC/base_model.py:79-108, the reference's class of the same name StackedAttentionModel): classifier(v_att(v, q_emb) +
+    va_att(v, a_emb)).  Registration order as the reference's (va_att before v_att), hence its state_dict order.  Inference: the two blocks
+    share v, so all their V-side projections are ONE GEMM."""
+
+    def __init__(self, w_emb, q_emb, wa_emb, a_emb, v_att, va_att, classifier):
+        super(MCStackedAttentionModel, self).__init__()
+        self.w_emb = w_emb
+        self.q_emb = q_emb
+        self.wa_emb = wa_emb
+        self.a_emb = a_emb
+        self.va_att = va_att
+        self.v_att = v_att
+        self.classifier = classifier
+        from .attention import _CatCache
+        object.__setattr__(self, "_c_v", _CatCache())
+
+    def forward(self, v, q, a):
+        v = _v_as_taken(v, self)
+        if v.dtype == torch.bfloat16:
+            v = ops.widen_bf16(v)                                            # (the attention blocks read fp32 rows)
+        q_emb = self.q_emb.forward_all(self.w_emb.rows16(q))[:, -1]
+        a_emb = self.a_emb.forward_all(self.wa_emb.rows16(a))[:, -1]
+        va, vb = self.v_att, self.va_att
+        shared = (v.is_cuda and v.dim() == 3 and not va._autograd_needed(v, q_emb) and not vb._autograd_needed(v, a_emb)
+                  and [tuple(w.shape) for w in va.v_weights()] == [tuple(w.shape) for w in vb.v_weights()])
+        if not shared:
+            return self.classifier(va(v, q_emb) + vb(v, a_emb))
+        B, N, Dv = v.shape
+        w, _, planes = self._c_v.get(va.v_weights() + vb.v_weights())
+        P_all = ops.gemm_nt(v.reshape(B * N, Dv), w, B_planes=planes)       # (B*N, 2 S A): both blocks' V-side projections in one launch
+        x = va._forward(v, q_emb, True, _projected=(P_all, 0))
+        y = vb._forward(v, a_emb, True, _projected=(P_all, va.num_stacks * va.att_size))
+        return self.classifier(ops.axpby(x, 1.0, y, 1.0, out=x))
+
+
+def build_san(args, dataset):
+    """src/FFOE/base_model.py:162-174 (no tf-idf initialisation: see the module docstring)."""
+    w_emb = WordEmbedding(dataset.dictionary.ntoken, 300, 0.0, args.op)
+    q_emb = QuestionEmbedding(300 if 'c' not in args.op else 600, args.num_hid, 1, False, 0.0)
+    v_att = StackedAttention(args.num_stacks, dataset.v_dim, args.num_hid, args.num_hid, dataset.num_ans_candidates, args.dropout)
+    classifier = SimpleClassifier(args.num_hid, 2 * args.num_hid, dataset.num_ans_candidates, args)
+    return StackedAttentionModel(w_emb, q_emb, v_att, classifier)
+
+
+def build_mc_san(args, dataset):
+    """src/MC/base_model.py:211-230 (`build_stacked_attention` of the MC package; its main.py looks up `build_san`, which that package does not
+    define): two StackedAttention blocks over v, one for the question and one for the answer, 2 output classes."""
+    w_emb = WordEmbedding(dataset.dictionary.ntoken, 300, 0.0, args.op)
+    q_emb = QuestionEmbedding(300 if 'c' not in args.op else 600, args.num_hid, 1, False, 0.0)
+    wa_emb = WordEmbedding(dataset.dictionary.ntoken, 300, 0.0, args.op)
+    a_emb = QuestionEmbedding(300 if 'c' not in args.op else 600, args.num_hid, 1, False, 0.0)
+    v_att = StackedAttention(args.num_stacks, dataset.v_dim, args.num_hid, args.num_hid, dataset.num_ans_candidates, args.dropout)
+    va_att = StackedAttention(args.num_stacks, dataset.v_dim, args.num_hid, args.num_hid, dataset.num_ans_candidates, args.dropout)
+    classifier = SimpleClassifier(args.num_hid, 2 * args.num_hid, 2, args)
+    return MCStackedAttentionModel(w_emb, q_emb, wa_emb, a_emb, v_att, va_att, classifier)

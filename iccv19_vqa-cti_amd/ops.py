@@ -1717,6 +1717,105 @@ def col_sum(x2, alpha=1.0):
     return out
 
 
+# ---- SAN attention step (src/attention.py:90-152; include/cti_hip.h: cti_san_attend_fwd / cti_san_attend_bwd) -------------------------
+def _bnd(x, name):
+    """(B, N, D) fp32 with unit column stride -> (x, row stride, sample stride); copies only when the layout is not a strided row block."""
+    _req(x, name)
+    if x.dim() != 3:
+        raise ValueError("%s must be (batch, rows, features), got %s" % (name, tuple(x.shape)))
+    B, N, D = x.shape
+    for attempt in range(2):
+        ld = x.stride(1) if N > 1 else D
+        sb = x.stride(0) if B > 1 else (N - 1) * ld + D
+        if x.stride(2) == 1 and ld >= D and sb >= (N - 1) * ld + D:
+            return x, ld, sb
+        x = x.contiguous()
+    raise AssertionError("unreachable")
+
+
+def _bd(x, name):
+    """(B, D) fp32 with unit column stride -> (x, row stride)."""
+    _req(x, name)
+    if x.dim() != 2:
+        raise ValueError("%s must be (batch, features), got %s" % (name, tuple(x.shape)))
+    if x.stride(1) != 1 or (x.shape[0] > 1 and x.stride(0) < x.shape[1]):
+        x = x.contiguous()
+    return x, (x.stride(0) if x.shape[0] > 1 else x.shape[1])
+
+
+def san_attend(P, qv, w, b, X=None, keep=None, p_drop=0.0, v_mask=True, out=None):
+    """One attention step of StackedAttention for every sample (cti_san_attend_fwd): P (B, N, A) the projected rows (a column slice of a batched
+    projection is read in place), qv (B, A), w (A,) / b (1,) the logit layer, X (B, N, Dx) the pool source (None: P itself), keep: None or a
+    uint8 (B, N, A) keep-mask drawn with dropout_mask(..., p_drop).  Returns (pooled (B, Dx), prob (B, N), logits (B, N)); out: a (B, Dx) view
+    with unit column stride to write pooled into."""
+    P, ldp, sP = _bnd(P, "P")
+    B, N, A = P.shape
+    qv, sq = _bd(qv, "qv")
+    _req(w, "w")
+    if b is not None:
+        _req(b, "b")
+    if tuple(qv.shape) != (B, A) or w.numel() != A or (b is not None and b.numel() != 1):
+        raise ValueError("san_attend: P %s, qv %s, w %d, b %s do not fit" % (tuple(P.shape), tuple(qv.shape), w.numel(), None if b is None else b.numel()))
+    w = w.contiguous().view(-1)
+    if X is None:
+        Xp, ldx, sX = P, ldp, sP
+    else:
+        Xp, ldx, sX = _bnd(X, "X")
+        if Xp.shape[:2] != P.shape[:2]:
+            raise ValueError("san_attend: X %s and P %s have different rows" % (tuple(Xp.shape), tuple(P.shape)))
+    Dx = Xp.shape[2]
+    if keep is not None:
+        _req(keep, "keep", torch.uint8)
+        if tuple(keep.shape) != (B, N, A) or not keep.is_contiguous():
+            raise ValueError("san_attend: keep must be a contiguous (B, N, A) mask")
+    logits = torch.empty((B, N), device=P.device, dtype=torch.float32)
+    prob = torch.empty((B, N), device=P.device, dtype=torch.float32)
+    if out is None:
+        out = torch.empty((B, Dx), device=P.device, dtype=torch.float32)
+    out2, ldo = _bd(out, "out")
+    if out2.data_ptr() != out.data_ptr() or tuple(out.shape) != (B, Dx):
+        raise ValueError("san_attend: out must be a (B, Dx) view with unit column stride")
+    if B == 0 or N == 0:
+        return out.zero_(), prob, logits
+    with _timed("san_attend_%dx%dx%dx%d" % (B, N, A, Dx)):
+        L.check(L.lib().cti_san_attend_fwd(P.data_ptr(), ldp, sP, qv.data_ptr(), sq, w.data_ptr(), _ptr(b), _ptr(keep), float(p_drop), int(bool(v_mask)),
+                                           Xp.data_ptr(), ldx, sX, logits.data_ptr(), prob.data_ptr(), out.data_ptr(), ldo, B, N, A, Dx, _stream()),
+                "cti_san_attend_fwd")
+    return out, prob, logits
+
+
+def san_attend_bwd(dpooled, P, qv, w, prob, X=None, keep=None, p_drop=0.0, need_dX=False):
+    """Backward of san_attend (cti_san_attend_bwd + two cti_col_sum reductions of the per-sample partials): returns (dP (B, N, A),
+    dqv (B, A), dw (A,), db (1,), dX (B, N, Dx) or None).  X None: the pool source was P, whose gradient then includes the pool's term."""
+    P, ldp, sP = _bnd(P, "P")
+    B, N, A = P.shape
+    qv, sq = _bd(qv, "qv")
+    dpooled, ldg = _bd(dpooled, "dpooled")
+    w = _req(w, "w").contiguous().view(-1)
+    prob = _req(prob, "prob").contiguous()
+    if X is None:
+        Xp, ldx, sX, Dx = None, 0, 0, A
+    else:
+        Xp, ldx, sX = _bnd(X, "X")
+        Dx = Xp.shape[2]
+    if tuple(dpooled.shape) != (B, Dx) or tuple(prob.shape) != (B, N) or tuple(qv.shape) != (B, A) or w.numel() != A:
+        raise ValueError("san_attend_bwd: shapes do not fit")
+    if keep is not None:
+        _req(keep, "keep", torch.uint8)
+    dev = P.device
+    dP = torch.empty((B, N, A), device=dev, dtype=torch.float32)
+    dqv = torch.empty((B, A), device=dev, dtype=torch.float32)
+    dw_part = torch.empty((B, A), device=dev, dtype=torch.float32)
+    db_part = torch.empty((B, 1), device=dev, dtype=torch.float32)
+    dlogit = torch.empty((B, N), device=dev, dtype=torch.float32)
+    dX = torch.empty((B, N, Dx), device=dev, dtype=torch.float32) if (need_dX and X is not None) else None
+    L.check(L.lib().cti_san_attend_bwd(P.data_ptr(), ldp, sP, qv.data_ptr(), sq, w.data_ptr(), _ptr(keep), float(p_drop), _ptr(Xp), ldx, sX,
+                                       int(X is None), prob.data_ptr(), dpooled.data_ptr(), ldg, dP.data_ptr(), A, N * A, dqv.data_ptr(), A,
+                                       dw_part.data_ptr(), db_part.data_ptr(), dlogit.data_ptr(), _ptr(dX), Dx, N * Dx, B, N, A, Dx, _stream()),
+            "cti_san_attend_bwd")
+    return dP, dqv, col_sum(dw_part), col_sum(db_part), dX
+
+
 # The GRU's persistent form (cti_gru.hip: all steps in ONE launch whose workgroups meet at counters) needs every one of its workgroups resident, so two such
 # launches must never share the device: callers that enable it keep their GRUs on ONE stream (base_model._TriModel), run_concurrently's sibling streams do not
 # get it, and a process that drives one device from several host threads should leave it off.  CTI_GRU_PERSISTENT=1 enables it (default off: see DESIGN.md,

@@ -665,6 +665,36 @@ int cti_kd_rows_fwd(const float* x, const float* knowledge, float* row_kl, int r
 int cti_kd_rows_bwd(const float* x, const float* knowledge, const float* upstream, float coef, float* dx, int rows, int n, float T,
                     float beta, void* stream);
 
+/* ---- SAN attention step  (src/attention.py:90-152, StackedAttention) ------------------------------------------------------------ */
+/* One workgroup per sample b < B.  P: the sample's projected rows at P + b*sP, N x A with row stride ldp (a column slice of a batched
+ * projection is fine); qv: the q-side vector at qv + b*sq (A); w: the logit weight (A); bias: device scalar (NULL = 0); keep: NULL or the
+ * uint8 dropout keep-mask (B, N, A) contiguous, kept h scaled by 1 / (1 - p_drop); X: the pool source at X + b*sX, N x Dx, row stride ldx
+ * (P itself or v).  Writes
+ *     logits[b,n] = bias + sum_a w[a] drop(tanh(qv[a] + P[n,a])), -inf where v_mask != 0 and every element of P[n,:] is +-0 (bit-exact, as
+ *                   cti_zero_row_mask; the reference masks on the PROJECTED rows)           (B, N) contiguous
+ *     prob[b,:]   = softmax(logits[b,:]) -- NaN in every entry of a sample whose rows are all masked, as torch.softmax  (B, N) contiguous
+ *     pooled[b,d] = sum_n prob[b,n] X[n,d]   at pooled + b*ldo                               (B, Dx)
+ * Any N, A, Dx >= 1 (float4 rows when widths, strides and pointers allow).  Allocates nothing and never synchronises (capturable).
+ * CTI_E_NULL: a required pointer is NULL; CTI_E_SHAPE: B, N, A or Dx < 1, a stride too small for its rows, p_drop outside [0, 1) with a keep-mask.
+ * Nothing is launched on an argument error. */
+int cti_san_attend_fwd(const float* P, int64_t ldp, int64_t sP, const float* qv, int64_t sq, const float* w, const float* bias,
+                       const uint8_t* keep, float p_drop, int v_mask, const float* X, int64_t ldx, int64_t sX,
+                       float* logits, float* prob, float* pooled, int64_t ldo, int B, int N, int A, int Dx, void* stream);
+/* Backward of cti_san_attend_fwd, one workgroup per sample: tanh is recomputed from P and qv; prob is the forward's output, dpooled (B, Dx)
+ * at dpooled + b*ldg the upstream gradient.  x_is_p != 0: the pool source is P itself (Dx == A; X, ldx, sX are ignored and dX must be NULL).
+ *     dlogit[b,n]  = prob[n] (dpooled . X[n,:] - sum_m prob[m] dpooled . X[m,:])            (B, N) contiguous
+ *     dP[b,n,a]    = dlogit[n] w[a] drop'(n,a) (1 - h^2) (+ prob[n] dpooled[a] when x_is_p)  at dP + b*sdP, row stride lddp
+ *     dqv[b,a]     = sum_n of the pre-tanh gradient                                        at dqv + b*sdq
+ *     dw_part[b,a] = sum_n dlogit[n] drop(h[n,a]);  db_part[b] = sum_n dlogit[n]            (B, A) contiguous, (B): per-sample partials,
+ *                    reduced over b by the caller (cti_col_sum)
+ *     dX[b,n,d]    = prob[n] dpooled[d]  at dX + b*sdX, row stride lddx -- only when dX != NULL
+ * Every sum runs in a fixed order (no float atomics): the gradients are bitwise reproducible from run to run.  Same error codes as the forward,
+ * plus CTI_E_SHAPE for x_is_p with Dx != A or a dX. */
+int cti_san_attend_bwd(const float* P, int64_t ldp, int64_t sP, const float* qv, int64_t sq, const float* w, const uint8_t* keep, float p_drop,
+                       const float* X, int64_t ldx, int64_t sX, int x_is_p, const float* prob, const float* dpooled, int64_t ldg,
+                       float* dP, int64_t lddp, int64_t sdP, float* dqv, int64_t sdq, float* dw_part, float* db_part, float* dlogit,
+                       float* dX, int64_t lddx, int64_t sdX, int B, int N, int A, int Dx, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

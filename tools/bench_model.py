@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """Model-level timings at the reference's real widths (rows N1, N3, N4 of 8f): full forward (eval) and
 one training step (forward + loss + backward + clipped Adamax through FlatAdamaxDP) of the FFOE CTI model, the FFOE BAN model
-(gamma = 8) and the MC CTI model, B = 256, random-init weights, synthetic inputs.  One JSON line per case.
+(gamma = 8), the MC CTI model and the two SAN models (2 stacks), B = 256, random-init weights, synthetic inputs.  One JSON line per case.
 
-    python tools/bench_model.py [ffoe_cti ffoe_ban mc_cti] [--train] [--steps 20] [--precision bf16x3|bf16|fp32]
+    python tools/bench_model.py [ffoe_cti ffoe_ban mc_cti mc_ban ffoe_san mc_san] [--train] [--steps 20] [--precision bf16x3|bf16|fp32]
 
 `--precision bf16` = plain bf16 products with fp32 accumulation (BASELINE configs[2], [3] name bf16): 1 MFMA per product instead of 3;
 its own tolerance is in tests/test_parity_gpu.py::test_plain_bf16_mode_within_its_own_tolerance.
@@ -31,7 +31,7 @@ class DS:
 
 def args_of(gamma):
     return types.SimpleNamespace(op="c", num_hid=1024, gamma=gamma, h_mm=512, rank=32, k=1, h_out=1, activation="relu", dropout=0.5,
-                                 use_counter=False)
+                                 use_counter=False, num_stacks=2)
 
 
 def tokens(B, L, ntoken, g):
@@ -47,6 +47,8 @@ CASES = {
     "ffoe_ban": ("build_ban", 8, 3129, 14, 0),
     "mc_cti": ("build_mc_cti", 2, 2, 12, 6),
     "mc_ban": ("build_mc_ban", 2, 2, 12, 6),
+    "ffoe_san": ("build_san", 0, 3129, 14, 0),
+    "mc_san": ("build_mc_san", 0, 2, 12, 6),
 }
 
 
@@ -71,6 +73,10 @@ def run(name, train, steps, warmup=5, B=256, ntoken=20000, around_timed=None):
             return m(v, boxes, q, None)[0]
         if name == "mc_ban":
             return m(v, boxes, q, a)[0]
+        if name == "ffoe_san":
+            return m(v, q)
+        if name == "mc_san":
+            return m(v, q, a)
         return m(v, boxes, q, a)[0]
 
     if train:
