@@ -1,6 +1,6 @@
 """iccv19_vqa-cti_amd -- MI355X-native Compact Trilinear Interaction hot path.
 
-Drop-in `nn.Module`s for the reference's TCNet / BCNet / BiAttention / TriAttention / FCNet / ModeProduct whose
+Drop-in `nn.Module`s for the reference's TCNet / BCNet / BiAttention / TriAttention / StackedAttention / Counter / FCNet / ModeProduct whose
 forward runs in hand-written gfx950 HIP kernels (csrc/) reached through the C ABI of include/cti_hip.h.
 The directory name carries a hyphen, so import it through the repo-root `cti_amd` module (or `dropin/src/*`)."""
 from . import _lib, ops, autograd                              # noqa: F401
@@ -8,6 +8,7 @@ from .fc import FCNet, WNLinear                                # noqa: F401
 from .tc import TCNet                                          # noqa: F401
 from .bc import BCNet                                          # noqa: F401
 from .attention import BiAttention, TriAttention, StackedAttention   # noqa: F401
+from .counting import Counter, PiecewiseLin                    # noqa: F401
 from .Tensor import ModeProduct                                # noqa: F401
 from .ops import set_precision, get_precision, invalidate_caches, set_range_check, f16f6_range_status, run_concurrently   # noqa: F401
 from ._lib import CtiError                                     # noqa: F401
@@ -21,7 +22,7 @@ from . import base_model                                       # noqa: F401
 from .base_model import BanModel, CTIModel, TanModel, MCBanModel, build_ban, build_cti, build_mc_cti, build_mc_ban   # noqa: F401
 from .base_model import StackedAttentionModel, MCStackedAttentionModel, build_san, build_mc_san   # noqa: F401
 
-__all__ = ["FCNet", "WNLinear", "TCNet", "BCNet", "BiAttention", "TriAttention", "StackedAttention", "ModeProduct",
+__all__ = ["FCNet", "WNLinear", "TCNet", "BCNet", "BiAttention", "TriAttention", "StackedAttention", "Counter", "PiecewiseLin", "ModeProduct",
            "ops", "set_precision", "get_precision", "invalidate_caches", "set_range_check", "f16f6_range_status", "CtiError", "FlatAdamaxDP", "GraphedTrainStep", "GraphedForward",
            "WordEmbedding", "QuestionEmbedding", "SimpleClassifier", "BCEWithLogitsSum", "Distillation_Loss", "base_model",
            "BanModel", "CTIModel", "TanModel", "MCBanModel", "build_ban", "build_cti", "build_mc_cti", "build_mc_ban",

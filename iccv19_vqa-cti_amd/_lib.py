@@ -151,6 +151,9 @@ SIGNATURES = {
                                   _int, _int, _int, _int, _vp]),
     "cti_san_attend_bwd": (_int, [_vp, _i64, _i64, _vp, _i64, _vp, _vp, C.c_float, _vp, _i64, _i64, _int, _vp, _vp, _i64,
                                   _vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _int, _int, _int, _int, _vp]),
+    "cti_counter_save_bytes": (_sz, [_i64]),
+    "cti_counter_fwd": (_int, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _int, _vp, _i64, _i64, _vp, _sz, _int, _int, _int, _int, _int, _int, _vp]),
+    "cti_counter_bwd": (_int, [_vp, _vp, _i64, _i64, _i64, _vp, _int, _vp, _sz, _vp, _vp, _int, _int, _int, _int, _int, _int, _vp]),
 }
 
 PREC_F32, PREC_BF16X3, PREC_BF16, PREC_F16F6 = 0, 1, 2, 3

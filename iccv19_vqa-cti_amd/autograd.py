@@ -76,6 +76,27 @@ class SanAttendFn(torch.autograd.Function):
         return dP, dqv, dw.view(w.shape), db if ctx.needs_input_grad[3] else None, dX, None, None, None
 
 
+class CounterFn(torch.autograd.Function):
+    """Counter.forward (src/counting.py:30-65) on an attention (B, V) or on a whole logit block (B, G, V, Q) reduced by max over Q, as
+    cti_counter_fwd / _bwd.  Gradients: the attention / logit block (dense, zero away from the selected boxes' arg-max positions) and the eight
+    weight vectors; boxes get none."""
+
+    @staticmethod
+    def forward(ctx, boxes, logits, objects, already_sigmoided, *weights):
+        out, save = ops.counter_fwd(boxes, logits, weights, objects, already_sigmoided)
+        ctx.save_for_backward(boxes, save, *weights)
+        ctx.cfg = (objects, already_sigmoided, tuple(logits.shape))
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        boxes, save = ctx.saved_tensors[:2]
+        weights = ctx.saved_tensors[2:]
+        objects, sig, shape = ctx.cfg
+        dlogits, dw = ops.counter_bwd(dout, boxes, weights, save, objects, shape, sig)
+        return (None, dlogits if ctx.needs_input_grad[1] else None, None, None) + tuple(dw[i].view(weights[i].shape) for i in range(8))
+
+
 class DropoutFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, p):

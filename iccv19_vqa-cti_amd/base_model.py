@@ -8,8 +8,14 @@ residual projections (`q_prj(b_emb.unsqueeze(1)) + q_emb` = one GEMM + one broad
 through a generic broadcast), the sequence sums and the classifier.
 
 The SAN baseline (src/FFOE/base_model.py:70-93,162-174; src/MC/base_model.py:79-108,211-230) is StackedAttentionModel /
-MCStackedAttentionModel with build_san / build_mc_san.  Outside the path (it raises): the counting module (`--use_counter`, src/counting.py); tf-idf
-initialisation of the embeddings (`tfidf_loading`, src/utils.py) is data preparation -- load a checkpoint or call
+MCStackedAttentionModel with build_san / build_mc_san.
+
+The counting module (`--use_counter`, src/counting.py) is counting.Counter: both BAN models take one (`counter=`), register `c_prj` in the
+reference's position when they have it, and compute the count features of ALL glimpses in one launch in front of the glimpse loop (the
+counter reads only `b` and the attention logits); c_prj[g] of them is a per-sample addend of the residual chain.  FFOE `build_ban` takes the
+counter as its third argument (the bare `args.use_counter` still raises there); `build_mc_ban` honours the flag.
+
+Outside the path: tf-idf initialisation of the embeddings (`tfidf_loading`, src/utils.py) is data preparation -- load a checkpoint or call
 `WordEmbedding.init_embedding`."""
 import contextlib
 import math
@@ -24,6 +30,7 @@ from . import ops
 from .attention import BiAttention, StackedAttention, TriAttention
 from .bc import BCNet
 from .classifier import SimpleClassifier
+from .counting import Counter
 from .fc import BatchedLinears, FCNet, HoistedProjection, WNLinear
 from .fc import refresh_stale_scales as _refresh_scales
 from .language_model import QuestionEmbedding, WordEmbedding
@@ -111,9 +118,22 @@ def _v_as_taken(v, module):
     return v
 
 
-def _no_counter(counter):
-    if counter is not None:
-        raise NotImplementedError("the counting module (src/counting.py, --use_counter) is outside the CTI path; build with counter=None")
+def _count_terms(self, b, logits):
+    """c_prj[g](counter(boxes, logits[:, g].max(2))) for every glimpse (src/FFOE/base_model.py:48,56-58,62): the count features of all glimpses come from
+    ONE launch (Counter.forward_logits), each projection is an (objects + 1) -> num_hid weight-normalised Linear + ReLU.  A list of (B, num_hid)."""
+    embed = self.counter.forward_logits(b, logits)                           # (B, G, objects + 1) on glimpse-major storage
+    lays = [HoistedProjection._layer_of(p) for p in self.c_prj]
+    if not _needs_grad(embed, *self.c_prj.parameters()) and not self.c_prj.training and all(l is not None for l in lays) and len(lays) > 1:
+        # inference: the G projections as ONE batched product on the G contiguous (B, objects + 1) blocks the counter wrote
+        if not hasattr(self, "_c_batch"):
+            object.__setattr__(self, "_c_batch", BatchedLinears(lays))
+        return list(self._c_batch.stacked(embed.permute(1, 0, 2), relu=True).unbind(0))
+    return [self.c_prj[g](e) for g, e in enumerate(embed.unbind(1))]
+
+
+def _add_count(q_emb, cnt):
+    """q_emb + cnt.unsqueeze(1)  (src/FFOE/base_model.py:62)."""
+    return AG.SeqBcastAddFn.apply(q_emb, cnt) if _needs_grad(q_emb, cnt) else ops.seq_bcast_add(q_emb, cnt)
 
 
 class BanModel(nn.Module):
@@ -121,7 +141,6 @@ class BanModel(nn.Module):
 
     def __init__(self, dataset, w_emb, q_emb, v_att, b_net, q_prj, c_prj, classifier, counter, op, glimpse):
         super(BanModel, self).__init__()
-        _no_counter(counter)
         self.dataset = dataset
         self.op = op
         self.glimpse = glimpse
@@ -130,6 +149,8 @@ class BanModel(nn.Module):
         self.v_att = v_att
         self.b_net = nn.ModuleList(b_net)
         self.q_prj = nn.ModuleList(q_prj)
+        if counter is not None:
+            self.c_prj = nn.ModuleList(c_prj)
         self.classifier = classifier
         self.counter = counter
         self._v_hoist = HoistedProjection([n.v_net for n in self.b_net])   # N1: one batched GEMM for the glimpses' v projections
@@ -163,16 +184,17 @@ class BanModel(nn.Module):
             att, logits = self.v_att.forward_all(v, q_emb)                  # b x g x v x q
             vp = self._v_hoist.maybe(v)
             Hq = self._hoist_prepare(q_emb, vp)
+        cnt = _count_terms(self, b, logits) if self.counter is not None else None      # (before the loop: the counter reads only b and the logits)
         try:
             hoisted = _ban_forward_unrolled(self, q_emb, att, vp, Hq) if _ban_unroll_ok(self, vp) else None
         except _UnrolledLoopLost:
             hoisted = None                        # -> the hoisted / literal loop recomputes the forward
         if hoisted is None:
-            hoisted = self._forward_hoisted(q_emb, att, vp, Hq)
+            hoisted = self._forward_hoisted(q_emb, att, vp, Hq, cnt)
         if hoisted is not None:
             return self.classifier(hoisted), att
         total = None
-        fused_sum = not torch.is_grad_enabled()
+        fused_sum = not torch.is_grad_enabled() and cnt is None            # (with a counter the glimpse's sum is taken behind the count term)
         if fused_sum:                                                        # inference: the per-glimpse sums accumulate inside the residual pass
             # (beta = 0 at g == 0 initialises it; with no glimpse at all the classifier must see zeros, not uninitialised memory: ADVICE r3)
             total = (torch.zeros if self.glimpse == 0 else torch.empty)(q_emb.shape[0], q_emb.shape[2], device=q_emb.device, dtype=torch.float32)
@@ -183,6 +205,8 @@ class BanModel(nn.Module):
                 q_emb = _residual(self.q_prj[g], b_emb, q_emb, acc=total, beta=1.0 if g > 0 else 0.0)
                 continue
             q_emb = _residual(self.q_prj[g], b_emb, q_emb)
+            if cnt is not None:
+                q_emb = _add_count(q_emb, cnt[g])
             # torch.stack(q_emb_list, 1).sum(1) then .sum(1): accumulate the per-glimpse sequence sums
             if _needs_grad(q_emb):
                 s = AG.SeqSumFn.apply(q_emb)
@@ -193,13 +217,15 @@ class BanModel(nn.Module):
         return logits, att
 
 
-def _ban_forward_hoisted(self, q_emb, att, vp, Hq):
+def _ban_forward_hoisted(self, q_emb, att, vp, Hq, cnt=None):
     """The glimpse loop of src/FFOE/base_model.py:53-64 without a (B*L, h) GEMM between two glimpses.  q_emb after glimpse g is q_emb_0 + D_g[:, None, :]
     (D_g = the sum of the residual projections so far, one vector per sample), and q_net_g is linear before its ReLU, so
         q_net_g(q_emb_g) = relu(H_g + (s_g W_g D_g)[:, None, :]),   H_g = s_g W_g q_emb_0 + bias_g:
     the H_g of ALL glimpses are one batched GEMM up front (like the v projections), the per-glimpse work on the dependent chain is a (B, h) GEMM, the pool
     (which forms relu(H + shift) as it loads the rows: cti_bi_pool_shift_fwd) and the residual projection; q_emb itself is never rebuilt.  The classifier
-    input sum_g q_emb_g.sum(1) is G * q_emb_0.sum(1) + L * sum_g D_g.  Returns it, or None when the form does not apply (the caller runs the literal loop)."""
+    input sum_g q_emb_g.sum(1) is G * q_emb_0.sum(1) + L * sum_g D_g.  Returns it, or None when the form does not apply (the caller runs the literal loop).
+    cnt (a model with a counter): the glimpses' count terms, per-sample constants of the chain -- D_{g+1} = D_g + cnt_g + q_prj_g(b_emb_g), added to D in
+    front of the residual projection so that both the next shift and the running sum E see them."""
     if Hq is None:
         return None
     nets = [n.q_net for n in self.b_net]
@@ -211,6 +237,8 @@ def _ban_forward_hoisted(self, q_emb, att, vp, Hq):
         b_emb = ops.bi_pool_shift(vp[g], Hq[g], _shift_of(lay, D) if g > 0 else None, att[:, g, :, :].float())
         if b_emb is None:
             return None                                                  # (only at g == 0: no kernel takes this shape with the on-load shift)
+        if cnt is not None:
+            D = cnt[g] if g == 0 else ops.axpby(D, 1.0, cnt[g], 1.0)
         out = ops.linear_residual(b_emb, lin.planes(), lin.scale(), lin.out_features, lin.bias, D.view(B, 1, H), acc=E, beta=1.0)
         if out is None:
             return None
@@ -223,8 +251,8 @@ _UNROLL = _os.environ.get("CTI_NO_UNROLLED_LOOP", "0") != "1"      # A/B knob
 
 def _ban_unroll_ok(self, vp):
     """The unrolled loop's preconditions beyond the hoisted loop's (checked there: Hq is not None): inference in a bf16 mode, at most 8 glimpses of split-K slabs
-    (32 addends per pool), every q_prj a single WNLinear."""
-    return (_UNROLL and vp is not None and not torch.is_grad_enabled() and ops.get_precision() != "fp32" and 2 <= self.glimpse <= 8
+    (32 addends per pool), every q_prj a single WNLinear, no counter (a model with one takes the hoisted loop: DESIGN.md section 7, "The counting module")."""
+    return (_UNROLL and self.counter is None and vp is not None and not torch.is_grad_enabled() and ops.get_precision() != "fp32" and 2 <= self.glimpse <= 8
             and all(_single_linear(p) is not None for p in self.q_prj) and all(HoistedProjection._layer_of(n.q_net) is not None for n in self.b_net))
 
 
@@ -616,7 +644,6 @@ class MCBanModel(nn.Module):
     def __init__(self, dataset, w_emb, q_emb, wa_emb, ans_emb, v_att, b_net, va_att, tva_net, q_prj, a_prj, c_prj, classifier, counter,
                  op, glimpse):
         super(MCBanModel, self).__init__()
-        _no_counter(counter)
         self.dataset = dataset
         self.op = op
         self.glimpse = glimpse
@@ -630,6 +657,8 @@ class MCBanModel(nn.Module):
         self.a_prj = nn.ModuleList(a_prj)
         self.va_att = va_att
         self.tva_net = nn.ModuleList(tva_net)
+        if counter is not None:
+            self.c_prj = nn.ModuleList(c_prj)
         self.classifier = classifier
         self.counter = counter
 
@@ -644,6 +673,7 @@ class MCBanModel(nn.Module):
             object.__setattr__(self, "_v_hoist", HoistedProjection([n.v_net for n in self.b_net] + [n.v_net for n in self.tva_net]))
         vp = self._v_hoist.maybe(v)
         G = self.glimpse
+        cnt = _count_terms(self, b, logits) if self.counter is not None else None
         for g in range(self.glimpse):
             w_g = att[:, g, :, :]
             b_emb = self.b_net[g].forward_with_weights(v, q_emb, w_g) if vp is None else self.b_net[g]._pool_projected(vp[g], q_emb, w_g)
@@ -652,6 +682,8 @@ class MCBanModel(nn.Module):
                       else self.tva_net[g]._pool_projected(vp[G + g], ans_emb, wa_g))
             q_emb = _residual(self.q_prj[g], b_emb, q_emb)
             ans_emb = _residual(self.a_prj[g], va_emb, ans_emb)
+            if cnt is not None:
+                q_emb = _add_count(q_emb, cnt[g])
         return self.classifier(_joint(q_emb, ans_emb)), att
 
 
@@ -664,8 +696,9 @@ def _embeddings(args, dataset, n):
     return out
 
 
-def build_ban(args, dataset):
-    """src/FFOE/base_model.py:139-160 (module construction order = the reference's, so the same seed gives the same parameters)."""
+def build_ban(args, dataset, counter=None):
+    """src/FFOE/base_model.py:139-160 (module construction order = the reference's, so the same seed gives the same parameters).  counter: the
+    model's counting module (cti_amd.Counter(10) is what the reference builds for `--use_counter`); the bare flag without it raises."""
     w_emb, q_emb = _embeddings(args, dataset, 1)
     v_att = BiAttention(dataset.v_dim, args.num_hid, args.num_hid, args.gamma)
     b_net, q_prj, c_prj = [], [], []
@@ -675,9 +708,10 @@ def build_ban(args, dataset):
         q_prj.append(FCNet([args.num_hid, args.num_hid], '', .2))
         c_prj.append(FCNet([objects + 1, args.num_hid], 'ReLU', .0))        # built (RNG stream) but only kept with a counter
     classifier = SimpleClassifier(args.num_hid, args.num_hid * 2, dataset.num_ans_candidates, args)
-    if getattr(args, 'use_counter', False):
-        _no_counter(True)
-    return BanModel(dataset, w_emb, q_emb, v_att, b_net, q_prj, c_prj, classifier, None, args.op, args.gamma)
+    if counter is None and getattr(args, 'use_counter', False):
+        raise NotImplementedError("FFOE build_ban does not build the counting module from args.use_counter alone; pass it: "
+                                  "build_ban(args, dataset, counter=cti_amd.Counter(10))")
+    return BanModel(dataset, w_emb, q_emb, v_att, b_net, q_prj, c_prj, classifier, counter, args.op, args.gamma)
 
 
 def _tri_parts(args, dataset, num_ans):
@@ -703,8 +737,8 @@ def build_mc_cti(args, dataset):
     return TanModel(dataset, *_tri_parts(args, dataset, 2), args.op, args.gamma)
 
 
-def build_mc_ban(args, dataset):
-    """src/MC/base_model.py:155-177 (`build_ban` of the MC package)."""
+def build_mc_ban(args, dataset, counter=None):
+    """src/MC/base_model.py:155-181 (`build_ban` of the MC package): `args.use_counter` builds Counter(10) as the reference does; counter: one to use instead."""
     w_emb, q_emb, wa_emb, ans_emb = _embeddings(args, dataset, 2)
     v_att = BiAttention(dataset.v_dim, args.num_hid, args.num_hid, args.gamma)
     va_att = BiAttention(dataset.v_dim, args.num_hid, args.num_hid, args.gamma)
@@ -717,9 +751,9 @@ def build_mc_ban(args, dataset):
         a_prj.append(FCNet([args.num_hid, args.num_hid], '', .2))
         c_prj.append(FCNet([objects + 1, args.num_hid], 'ReLU', .0))
     classifier = SimpleClassifier(args.num_hid, args.num_hid * 2, 2, args)
-    if getattr(args, 'use_counter', False):
-        _no_counter(True)
-    return MCBanModel(dataset, w_emb, q_emb, wa_emb, ans_emb, v_att, b_net, va_att, tva_net, q_prj, a_prj, c_prj, classifier, None,
+    if counter is None and getattr(args, 'use_counter', False):
+        counter = Counter(objects)
+    return MCBanModel(dataset, w_emb, q_emb, wa_emb, ans_emb, v_att, b_net, va_att, tva_net, q_prj, a_prj, c_prj, classifier, counter,
                       args.op, args.gamma)
 
 

@@ -115,10 +115,14 @@ class GraphedForward:
                 self.fn(*self.static_in)
             torch.cuda.synchronize(dev)
             self.graph = torch.cuda.CUDAGraph()
+            copies = ops._guard_block_copies[0]
             with torch.cuda.graph(self.graph, stream=s):
                 self.static_out = self.fn(*self.static_in)
+            guarded = ops._guard_block_copies[0] > copies
         torch.cuda.current_stream(dev).wait_stream(s)
-        self._blk = ops._guard_status_block.get(dev.index if dev.index is not None else torch.cuda.current_device())
+        # (only a graph that holds a guarded call rewrites the status block: after a replay of any other forward -- the BAN / SAN models, a mode other than
+        # f16f6 -- the block still holds what the process's LAST guarded call left there, which says nothing about this replay)
+        self._blk = ops._guard_status_block.get(dev.index if dev.index is not None else torch.cuda.current_device()) if guarded else None
         self._host = torch.zeros(1, dtype=torch.int32).pin_memory() if self._blk is not None else None
         self._ev = torch.cuda.Event()
 

@@ -93,6 +93,7 @@ def set_cancel_thresholds(bf16x3=2.75, fp32=5.5):
 # as the process (a reference to the workspace itself pinned GBs and kept the caching allocator from recycling the block).  Under graph capture the
 # copy is a node of the graph, so after a replay the tensor holds what THAT replay found.
 _guard_status_block = {}
+_guard_block_copies = [0]          # copies issued so far: graph.GraphedForward learns from it whether the forward it captured holds a guarded call at all
 
 
 def _keep_guard_block(ws):
@@ -103,6 +104,7 @@ def _keep_guard_block(ws):
             return                        # (memory born under capture belongs to that graph's pool; an eager guarded call -- any warm-up -- creates the block)
         blk = _guard_status_block[key] = torch.zeros(256, device=ws.device, dtype=torch.uint8)
     blk.copy_(ws[:256], non_blocking=True)
+    _guard_block_copies[0] += 1
 
 
 def f16f6_device_status(device=None, sync=True):
@@ -1814,6 +1816,93 @@ def san_attend_bwd(dpooled, P, qv, w, prob, X=None, keep=None, p_drop=0.0, need_
                                        dw_part.data_ptr(), db_part.data_ptr(), dlogit.data_ptr(), _ptr(dX), Dx, N * Dx, B, N, A, Dx, _stream()),
             "cti_san_attend_bwd")
     return dP, dqv, col_sum(dw_part), col_sum(db_part), dX
+
+
+# ---- counting module (src/counting.py:30-145; include/cti_hip.h: cti_counter_fwd / cti_counter_bwd) ----------------------------------------
+def _counter_weights(weights, n):
+    import ctypes as C
+    if len(weights) != 8:
+        raise ValueError("the counter has eight piecewise-linear functions, got %d weight vectors" % len(weights))
+    ws = []
+    for i, w in enumerate(weights):
+        _req(w, "weights[%d]" % i)
+        if w.numel() != n + 1:
+            raise ValueError("weights[%d] has %d elements, a function of %d segments has %d" % (i, w.numel(), n, n + 1))
+        ws.append(w if w.is_contiguous() else w.contiguous())
+    return ws, (C.c_void_p * 8)(*[w.data_ptr() for w in ws])
+
+
+def _counter_boxes(boxes):
+    """(B, 4, V) fp32 in ANY strides (the models pass `b[:, :, :4].transpose(1, 2)`: read in place)."""
+    _req(boxes, "boxes")
+    if boxes.dim() != 3 or boxes.shape[1] != 4:
+        raise ValueError("boxes must be (batch, 4, boxes), got %s" % (tuple(boxes.shape),))
+    if any(s < 0 for s in boxes.stride()):
+        boxes = boxes.contiguous()
+    return boxes
+
+
+def counter_fwd(boxes, logits, weights, objects, already_sigmoided=False, n=16):
+    """Counter.forward for every (sample, glimpse) row in ONE launch (cti_counter_fwd).  boxes (B, 4, V); logits: the attention (B, V), or a logit
+    block (B, G, V, Q) whose per-box score is its maximum over Q (`logits[:, g].max(2)` of the models) -- any strides, read in place; weights: the
+    eight raw (n + 1,) weight vectors.  Returns (out (B, objects + 1) or (B, G, objects + 1), save block for counter_bwd).  The (B, G, objects + 1) result is a
+    view of glimpse-major storage: `out.unbind(1)` / `out.permute(1, 0, 2)` are contiguous (the input of the models' batched count projection).  Ties in the
+    top-`objects` selection go to the lower box index."""
+    boxes = _counter_boxes(boxes)
+    _req(logits, "attention")
+    B, _, V = boxes.shape
+    if logits.dim() == 2:
+        G, Q, shape = 1, 1, (B, objects + 1)
+        sL = (logits.stride(0), 0, logits.stride(1), 0)
+    elif logits.dim() == 4:
+        G, Q, shape = logits.shape[1], logits.shape[3], (B, logits.shape[1], objects + 1)
+        sL = tuple(logits.stride())
+    else:
+        raise ValueError("the attention must be (batch, boxes) or a (batch, glimpses, boxes, q) logit block, got %s" % (tuple(logits.shape),))
+    if logits.shape[0] != B or logits.shape[-1 if logits.dim() == 2 else 2] != V:
+        raise ValueError("boxes %s and attention %s do not fit" % (tuple(boxes.shape), tuple(logits.shape)))
+    if V < objects:
+        raise ValueError("the counter keeps the %d boxes with the highest attention, got only %d (the reference fails in topk)" % (objects, V))
+    if any(s < 0 for s in sL):
+        logits = logits.contiguous()
+        sL = (logits.stride(0), 0, logits.stride(1), 0) if logits.dim() == 2 else tuple(logits.stride())
+    ws, wptr = _counter_weights(weights, n)
+    lib = L.lib()
+    m1 = objects + 1
+    if logits.dim() == 2:
+        out, sO = torch.empty(shape, device=boxes.device, dtype=torch.float32), (m1, m1)
+    else:
+        out, sO = torch.empty((G, B, m1), device=boxes.device, dtype=torch.float32).permute(1, 0, 2), (m1, B * m1)
+    nsave = lib.cti_counter_save_bytes(B * G)
+    save = torch.empty(max(nsave, 4) // 4, device=boxes.device, dtype=torch.int32)
+    if B * G == 0:
+        return out, save
+    with _timed("counter_fwd_%dx%dx%d" % (B * G, V, Q)):
+        L.check(lib.cti_counter_fwd(logits.data_ptr(), sL[0], sL[1], sL[2], sL[3], boxes.data_ptr(), boxes.stride(0), boxes.stride(1), boxes.stride(2), wptr,
+                                    int(bool(already_sigmoided)), out.data_ptr(), sO[0], sO[1], save.data_ptr(), nsave, B, G, V, Q, int(objects), int(n), _stream()),
+                "cti_counter_fwd")
+    return out, save
+
+
+def counter_bwd(dout, boxes, weights, save, objects, logits_shape, already_sigmoided=False, n=16):
+    """Backward of counter_fwd (cti_counter_bwd + one cti_col_sum over the per-row partials): returns (dlogits, dense and contiguous in
+    `logits_shape`, zero except at the selected boxes' arg-max positions; dweights (8, n + 1))."""
+    boxes = _counter_boxes(boxes)
+    B, _, V = boxes.shape
+    G, Q = (1, 1) if len(logits_shape) == 2 else (logits_shape[1], logits_shape[3])
+    dout = _req(dout, "dout").contiguous()
+    if dout.numel() != B * G * (objects + 1):
+        raise ValueError("counter_bwd: dout %s for %d rows of %d" % (tuple(dout.shape), B * G, objects + 1))
+    ws, wptr = _counter_weights(weights, n)
+    _req(save, "save", torch.int32)
+    dev = boxes.device
+    dlogits = torch.empty(tuple(logits_shape), device=dev, dtype=torch.float32)
+    dw_part = torch.empty((B * G, 8 * (n + 1)), device=dev, dtype=torch.float32)
+    with _timed("counter_bwd_%dx%dx%d" % (B * G, V, Q)):
+        L.check(L.lib().cti_counter_bwd(dout.data_ptr(), boxes.data_ptr(), boxes.stride(0), boxes.stride(1), boxes.stride(2), wptr, int(bool(already_sigmoided)),
+                                        save.data_ptr(), save.numel() * 4, dlogits.data_ptr(), dw_part.data_ptr(), B, G, V, Q, int(objects), int(n), _stream()),
+                "cti_counter_bwd")
+    return dlogits, col_sum(dw_part).view(8, n + 1)
 
 
 # The GRU's persistent form (cti_gru.hip: all steps in ONE launch whose workgroups meet at counters) needs every one of its workgroups resident, so two such

@@ -695,6 +695,35 @@ int cti_san_attend_bwd(const float* P, int64_t ldp, int64_t sP, const float* qv,
                        float* dP, int64_t lddp, int64_t sdP, float* dqv, int64_t sdq, float* dw_part, float* db_part, float* dlogit,
                        float* dX, int64_t lddx, int64_t sdX, int B, int N, int A, int Dx, void* stream);
 
+/* ---- counting module  (src/counting.py:30-145, Counter + PiecewiseLin; src/FFOE/base_model.py:56-58) ------------------------------- */
+/* One workgroup per row = (sample b < B, glimpse g < G) pair, rows = B * G.  logits: element (b, g, v, q) at logits + b*sLb + g*sLg + v*sLv + q*sLq
+ * (the models' (B, G, V, Q) logit block, or a `logits[:, g]` slice with G = 1; Q = 1 with a (B, V) attention is the plain module call);
+ * boxes: element (b, c, v), c < 4, at boxes + b*sBb + c*sBc + v*sBv (the reference's `b[:, :, :4].transpose(1, 2)` view or (B, 4, V) rows as they
+ * stand; one sample's boxes serve its G rows); weights: a HOST array of eight device pointers, the raw (n + 1) weights of f_0 .. f_7.
+ *     score[v]   = max_q logits[b, g, v, q]            (arg-max: the first maximum)
+ *     top `objects` of score over v; ties go to the LOWER box index
+ *     out[b,g,:] = Counter.forward on the selected boxes and scores (sigmoid first unless already_sigmoided), objects + 1 values at
+ *                  out + b*sOb + g*sOg: sample-major (sOb = G * (objects + 1), sOg = objects + 1) or glimpse-major (sOg = B * (objects + 1),
+ *                  sOb = objects + 1: one contiguous (B, objects + 1) block per glimpse, the input of a batched projection)
+ *     save       = per row: selected box indices, arg-max positions, the (sigmoided) scores: cti_counter_save_bytes(rows) bytes
+ * The piecewise-linear functions are evaluated from the raw weights by the reference's formula for any weights (signs, weight[0] != 0).
+ * 1 <= objects <= 16 and n == 16, else CTI_E_UNSUPPORTED; also V > 8192.  V < objects: CTI_E_SHAPE (the reference fails in topk).
+ * CTI_E_NULL: a required pointer (or one of the eight weights) is NULL; CTI_E_SHAPE: a size < 1, a negative stride, output strides whose rows would
+ * overlap; CTI_E_WORKSPACE: save block
+ * too small.  No atomics, nothing allocated or synchronised (capturable); nothing is launched on an argument error. */
+size_t cti_counter_save_bytes(int64_t rows);
+int cti_counter_fwd(const float* logits, int64_t sLb, int64_t sLg, int64_t sLv, int64_t sLq, const float* boxes, int64_t sBb, int64_t sBc, int64_t sBv,
+                    const float* const* weights, int already_sigmoided, float* out, int64_t sOb, int64_t sOg, void* save, size_t save_bytes, int B, int G,
+                    int V, int Q, int objects, int n, void* stream);
+/* Backward of cti_counter_fwd from its save block (the forward is recomputed on the selected boxes): dout (rows, objects + 1) contiguous.
+ *     dlogits (rows, V, Q) contiguous, written densely: zero except at (selected box, its arg-max position), as autograd's max(2) and topk give it
+ *     dw_part (rows, 8, n + 1): per-row partials of the weight gradients, reduced over the rows by the caller (cti_col_sum)
+ * Autograd's conventions at the kinks: |x|' = 0 at 0, clamp passes the gradient on its bounds, frac' = 1, no gradient through trunc / gathers;
+ * a factor of the (m, m, m) product gets the product of the other m - 1 factors (no division).  Boxes get no gradient.  Every sum runs in a fixed
+ * order: bitwise reproducible.  Same error codes as the forward. */
+int cti_counter_bwd(const float* dout, const float* boxes, int64_t sBb, int64_t sBc, int64_t sBv, const float* const* weights, int already_sigmoided,
+                    const void* save, size_t save_bytes, float* dlogits, float* dw_part, int B, int G, int V, int Q, int objects, int n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,8 +2,11 @@
 """Model-level timings at the reference's real widths (rows N1, N3, N4 of 8f): full forward (eval) and
 one training step (forward + loss + backward + clipped Adamax through FlatAdamaxDP) of the FFOE CTI model, the FFOE BAN model
 (gamma = 8), the MC CTI model and the two SAN models (2 stacks), B = 256, random-init weights, synthetic inputs.  One JSON line per case.
+`ffoe_ban_cnt` / `mc_ban_cnt`: the two BAN models with the counting module (Counter(10), `--use_counter`); the counter's cost is the
+difference to `ffoe_ban` / `mc_ban` of the same run.
 
-    python tools/bench_model.py [ffoe_cti ffoe_ban mc_cti mc_ban ffoe_san mc_san] [--train] [--steps 20] [--precision bf16x3|bf16|fp32]
+    python tools/bench_model.py [ffoe_cti ffoe_ban ffoe_ban_cnt mc_cti mc_ban mc_ban_cnt ffoe_san mc_san] [--train] [--steps 20]
+                                [--precision bf16x3|bf16|fp32]
 
 `--precision bf16` = plain bf16 products with fp32 accumulation (BASELINE configs[2], [3] name bf16): 1 MFMA per product instead of 3;
 its own tolerance is in tests/test_parity_gpu.py::test_plain_bf16_mode_within_its_own_tolerance.
@@ -47,6 +50,8 @@ CASES = {
     "ffoe_ban": ("build_ban", 8, 3129, 14, 0),
     "mc_cti": ("build_mc_cti", 2, 2, 12, 6),
     "mc_ban": ("build_mc_ban", 2, 2, 12, 6),
+    "ffoe_ban_cnt": ("build_ban", 8, 3129, 14, 0),
+    "mc_ban_cnt": ("build_mc_ban", 2, 2, 12, 6),
     "ffoe_san": ("build_san", 0, 3129, 14, 0),
     "mc_san": ("build_mc_san", 0, 2, 12, 6),
 }
@@ -55,7 +60,8 @@ CASES = {
 def run(name, train, steps, warmup=5, B=256, ntoken=20000, around_timed=None):
     builder, gamma, num_ans, Q, A = CASES[name]
     torch.manual_seed(1204)
-    m = getattr(cti_amd, builder)(args_of(gamma), DS(ntoken, 2048, num_ans)).to(DEV)
+    counter = {"counter": cti_amd.Counter(10)} if name.endswith("_cnt") else {}
+    m = getattr(cti_amd, builder)(args_of(gamma), DS(ntoken, 2048, num_ans), **counter).to(DEV)
     g = torch.Generator().manual_seed(7)
     v = torch.randn(B, 36, 2048, generator=g).abs()
     nv = torch.randint(10, 37, (B,), generator=g)
@@ -63,15 +69,20 @@ def run(name, train, steps, warmup=5, B=256, ntoken=20000, around_timed=None):
     v = v.to(DEV)
     q = tokens(B, Q, ntoken, g).to(DEV)
     a = tokens(B, A, ntoken, g).to(DEV) if A else None
-    boxes = torch.rand(B, 36, 6, generator=g).to(DEV)
+    boxes = torch.rand(B, 36, 6, generator=g)
+    if counter:                                               # proper boxes (x1 < x2, y1 < y2), zero rows behind the real ones
+        boxes[:, :, 2:4] = boxes[:, :, :2] * 0.6 + 0.05 + 0.35 * boxes[:, :, 2:4]
+        boxes[:, :, :2] *= 0.6
+        boxes[torch.arange(36)[None, :] >= nv[:, None]] = 0
+    boxes = boxes.to(DEV)
     tgt = ((torch.rand(B, num_ans, generator=g) < 0.01).float() * torch.rand(B, num_ans, generator=g)).to(DEV)
 
     def fwd():
         if name == "ffoe_cti":
             return m(v, q, a)
-        if name == "ffoe_ban":
+        if name in ("ffoe_ban", "ffoe_ban_cnt"):
             return m(v, boxes, q, None)[0]
-        if name == "mc_ban":
+        if name in ("mc_ban", "mc_ban_cnt"):
             return m(v, boxes, q, a)[0]
         if name == "ffoe_san":
             return m(v, q)
