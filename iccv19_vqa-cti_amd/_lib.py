@@ -161,6 +161,7 @@ E_UNSUPPORTED = -4                                   # CTI_E_UNSUPPORTED: shape 
 ACT_NONE, ACT_RELU = 0, 1
 TUNE_GEMM_CFG, TUNE_TRI_CHUNK = 1, 2                # cti_set_tuning keys
 TUNE_GUARD_RHO_BF16X3, TUNE_GUARD_RHO_FP32, TUNE_GUARD_POISON_BITS, TUNE_F6_CORE_FREE_CUS, TUNE_GUARD_STRATA, TUNE_GEMM16_SK, TUNE_GRU_PERSISTENT = 3, 4, 5, 6, 7, 8, 9     # f16f6 guard policy (include/cti_hip.h)
+TUNE_LAST_GEMM_ROUTE, TUNE_GEMM16_LAUNCHES = 10, 11    # read-only: which kernel the thread's last plane GEMM launched (ops.last_gemm_route() unpacks it); how many went to cti_gemm16.hip
 GUARD_SATURATED, GUARD_UNDERFLOW, GUARD_NONFINITE = 1, 2, 4     # status bits of the f16f6 range guard (cti_guard_read)
 
 _lib = None

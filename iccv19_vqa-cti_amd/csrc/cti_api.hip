@@ -28,7 +28,15 @@ static thread_local int g_guard_strata = 1;                       // test knob: 
 static thread_local int g_gemm16_sk = -1;                          // stream-K cut of the plain-bf16 row GEMM: -1 = where it was measured to pay (three or more rounds of tiles), 0 = never, 1 = wherever it can be planned
 static thread_local int g_gru_persistent = 0;                      // 1 = cti_gru_forward may run all steps of an eligible call as ONE persistent launch (the caller keeps two of them off the chip at once)
 static thread_local int g_f6_core_free_cus = -1;                  // CUs the mode-3 product leaves to the guard kernels beside it (-1 = the library's default)
+static thread_local int g_gemm_route = 0;                         // key 10: the last plane GEMM's route (0 = none yet)
 int tuning_gemm_cfg() { return g_gemm_cfg; }
+static thread_local unsigned g_gemm16_launches = 0;                // key 11: ... and how many of them went to cti_gemm16.hip
+void note_gemm_route(int kernel, int cfg, int a_form, int epi) {
+    g_gemm_route = kernel | ((cfg & 15) << 4) | (a_form << 8) | ((epi & 15) << 12);
+    if (kernel == GEMM_ROUTE_GEMM16) ++g_gemm16_launches;
+}
+void note_gemm_route_split_k() { g_gemm_route |= GEMM_ROUTE_SPLIT_K; }
+int64_t last_gemm_route() { return g_gemm_route; }
 int64_t tuning_tri_chunk() { return (int64_t)g_tri_chunk; }
 float tuning_guard_rho(int which) { return 1e-3f * (float)g_guard_rho_milli[which ? 1 : 0]; }
 unsigned tuning_guard_poison_bits() { return (unsigned)g_guard_poison_bits; }
@@ -69,6 +77,8 @@ extern "C" int cti_set_tuning(int key, int64_t value) {
         case CTI_TUNE_GRU_PERSISTENT:
             CTI_REQUIRE(value >= 0 && value <= 2, CTI_E_SHAPE, "cti_set_tuning: GRU_PERSISTENT must be 0, 1 or 2, got %lld", (long long)value);
             g_gru_persistent = (int)value; return CTI_OK;
+        case CTI_TUNE_LAST_GEMM_ROUTE:
+        case CTI_TUNE_GEMM16_LAUNCHES: return fail(CTI_E_UNSUPPORTED, "cti_set_tuning: key %d is read-only", key);
         default: return fail(CTI_E_UNSUPPORTED, "cti_set_tuning: unknown key %d", key);
     }
 }
@@ -83,6 +93,8 @@ extern "C" int64_t cti_get_tuning(int key) {
         case CTI_TUNE_GUARD_STRATA: return g_guard_strata;
         case CTI_TUNE_GEMM16_SK: return g_gemm16_sk;
         case CTI_TUNE_GRU_PERSISTENT: return g_gru_persistent;
+        case CTI_TUNE_LAST_GEMM_ROUTE: return last_gemm_route();
+        case CTI_TUNE_GEMM16_LAUNCHES: return (int64_t)g_gemm16_launches;
         default: return INT64_MIN;
     }
 }

@@ -629,9 +629,11 @@ static int gemm_bf16_rows_impl(const char* who, const void* A_bf16, int64_t lda,
     g.C = static_cast<float*>(C); g.ldc_m = ldc_m; g.ldc_n = 1; g.sC1 = sC1;
     g.scale = scale; g.scale_div = scale ? scale_div : 1; g.bias = bias; g.relu = act == CTI_ACT_RELU; g.scale_bs = scale_bs; g.bias_bs = bias_bs;
     g.sk_ws = workspace; g.sk_ws_bytes = workspace ? workspace_bytes : 0;
-    CTI_REQUIRE(gemm16_eligible(g), CTI_E_ALIGN, "%s: A needs 16-B aligned rows (lda %% 8 == 0), C rows of a multiple of 4 elements at a %d-B aligned origin, K / 32 >= 4 with bias or scale",
-                who, c_bf16 ? 8 : 16);
-    return gemm16_planes(g, as_stream(stream));
+    // the 256 x 256 tile unless a test forces one of the small ones (cti_set_tuning(CTI_TUNE_GEMM_CFG, 0 / 1); whole tiles only: those geometries take no stream-K workspace)
+    const int cfg = (tuning_gemm_cfg() == 0 || tuning_gemm_cfg() == 1) ? tuning_gemm_cfg() : 2;
+    CTI_REQUIRE(gemm16_eligible(g, cfg), CTI_E_ALIGN, "%s: A needs 16-B aligned rows (lda %% 8 == 0), C rows of a multiple of 4 elements at a %d-B aligned origin, K / 32 >= %d with bias or scale",
+                who, c_bf16 ? 8 : 16, cfg == 0 ? 8 : cfg == 1 ? 6 : 4);
+    return gemm16_planes(g, as_stream(stream), cfg);
 }
 
 extern "C" int cti_gemm_bf16_rows(const void* A_bf16, int64_t lda, int64_t rowsA_total, int64_t rA1, const void* B_planes, int64_t rowsB_total, int64_t rB1,

@@ -25,6 +25,12 @@ int tuning_guard_strata();            // key 7 (tests): 0 = the cancellation est
 int tuning_gru_persistent();          // key 9: 1 = cti_gru_forward may use its persistent form (cti_gru.hip)
 int tuning_gemm16_sk();               // key 8: stream-K cut of cti_gemm16.hip's row products (-1 auto, 0 never, 1 wherever plannable)
 int tuning_f6_core_free_cus();        // key 6: CUs the mode-3 product leaves free for the guard kernels beside it (-1 = default)
+// key 10 (read-only; the layout is in include/cti_hip.h): which kernel this thread's last plane GEMM launched.  kernel: 1 = cti_gemm16.hip, 2 = the planes kernel of
+// cti_gemm_bf16x3.hip, 3 = cti_gemm_skinny.hip; a_form: 0 planes, 1 bf16 rows, 2 fp32 rows.  One thread-local store per call (and key 11's count of the cti_gemm16.hip ones).
+enum { GEMM_ROUTE_GEMM16 = 1, GEMM_ROUTE_PLANES = 2, GEMM_ROUTE_SKINNY = 3, GEMM_ROUTE_SPLIT_K = 1 << 16 };
+void note_gemm_route(int kernel, int cfg, int a_form, int epi);
+void note_gemm_route_split_k();       // the route just noted was the inner product of a split-K: partials + ksplit_reduce_kernel
+int64_t last_gemm_route();
 
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
@@ -137,7 +143,8 @@ int split_planes(const float* x, int64_t ld, int64_t rows, int K, unsigned short
 int split_planes16(const unsigned short* x, int64_t ld, int64_t rows, int K, unsigned short* hi, unsigned short* lo, int64_t rows_alloc, hipStream_t st);   // bf16 rows -> planes (lo = 0)
 int gemm_nt_planes(const PlaneGemmArgs& a, hipStream_t st);
 // cti_gemm16.hip: the plain-bf16 (terms = 1) products of the 256 x 256 tile with fp32-row or planes epilogues
-bool gemm16_eligible(const PlaneGemmArgs& a);
+// (cfg: the tile the caller will launch with; -1 = not known yet: the strictest rule, so that the product is taken whatever tile gemm_nt_planes() picks)
+bool gemm16_eligible(const PlaneGemmArgs& a, int cfg = -1);
 int gemm16_planes(const PlaneGemmArgs& a, hipStream_t st, int cfg = 2);      // cfg: the tile of gemm_nt_planes()'s model (0 = 128 x 128, 1 = 256 x 128, 2 = 256 x 256)
 size_t gemm16_sk_workspace_bytes();
 // cti_gemm_skinny.hip: few rows x long K (what callers plan a split-K for) as ONE launch: K split over a workgroup's waves, partial tiles summed in LDS

@@ -523,10 +523,15 @@ size_t gemm16_sk_workspace_bytes() {
 }
 
 // Takes the plain-bf16 products gemm_nt_planes() would run on its 256 x 256 tile; false = not eligible (the caller's own kernel runs)
-bool gemm16_eligible(const PlaneGemmArgs& a) {
+bool gemm16_eligible(const PlaneGemmArgs& a, int cfg) {
     if (a.terms != 1 || a.Af || !(a.epi == 0 || a.epi == 1 || a.epi == 5) || a.ksplit > 1) return false;
     if (a.Kp % 32 != 0 || a.Kp <= 0) return false;
-    if ((a.bias || a.scale) && a.Kp / 32 < 4) return false;                 // the epilogue constants' double buffer assumes tiles of at least 4 stages
+    // the epilogue constants' double buffer: piece p + 2's constants are DMA'd over piece p's when the issue side -- NS - 1 stages ahead of the compute side -- opens
+    // piece p + 2, at interval 2 nk - (NS - 1) of piece p's first; piece p's epilogue reads them at interval nk.  Still piece p's only if nk >= NS: the ring depth of
+    // the tile that will run (cfg -1 = not known yet: the deepest ring's)
+    const int ns = cfg == 2 ? G16Sq::NS : cfg == 1 ? G16Tall::NS : G16Small::NS;
+    static_assert(G16Wide::NS == G16Sq::NS && G16Small::NS >= G16Tall::NS && G16Tall::NS >= G16Sq::NS, "cfg 2 covers both of its tiles; -1 is the strictest");
+    if ((a.bias || a.scale) && a.Kp / 32 < ns) return false;
     const int64_t rowsA = a.rows_allocA, rowsB = a.rows_allocB;
     if (rowsB * 32 * (int64_t)(a.Kp / 16) >= (1ll << 32)) return false;      // 32-bit per-lane offsets inside a plane
     if (a.Abf) {
@@ -553,6 +558,7 @@ int gemm16_planes(const PlaneGemmArgs& a, hipStream_t st, int cfg) {
     p.nb2 = a.nb2 > 0 ? a.nb2 : 1; p.M = a.M; p.N = a.N; p.Np = a.Np; p.nk = a.Kp / 32; p.scale_div = a.scale_div > 0 ? a.scale_div : 1; p.relu = a.relu;
     const int ncols = a.epi == 1 ? a.Np : a.N;
     const int nb = a.nb1 * p.nb2;
+    note_gemm_route(GEMM_ROUTE_GEMM16, cfg, a.Abf ? 1 : 0, a.epi);
     // cfg 0 / 1 (round 6): the 128 x 128 and 256 x 128 tiles of gemm_nt_planes()'s makespan model on THIS kernel -- the same two-group loop, 2 or 3 LDS-DMA pieces per wave
     // and stage.  The 128 x 128 planes kernel of cti_gemm_bf16x3.hip took ~0.6 us per 32-deep stage with one product per pair (a barrier round per stage for 4
     // MFMAs a wave): 3072 x 1024 x 1024 x 2 batches 38 us.

@@ -811,7 +811,7 @@ int gemm_nt_planes(const PlaneGemmArgs& a, hipStream_t st) {
                        a.ksplit, a.Af != nullptr, a.Abf != nullptr, a.scale != nullptr, a.bias != nullptr, a.relu);
     // round 6: a product its caller planned a split-K for (few rows, long K) is ONE launch of cti_gemm_skinny.hip instead of K ranges + partials + a reduce launch
     // (CTI_GEMM_SKINNY=0: off, A/B; a forced tile geometry -- the tests' cti_set_tuning -- keeps the split-K path reachable)
-    if ((a.ksplit > 1 || a.M <= 512) && tuning_gemm_cfg() < 0 && gemm_skinny_eligible(a)) return gemm_skinny(a, st);     // (any product of at most 512 rows: planned split or not)
+    if ((a.ksplit > 1 || a.M <= 512) && tuning_gemm_cfg() < 0 && gemm_skinny_eligible(a)) { note_gemm_route(GEMM_ROUTE_SKINNY, 15, a.Af ? 2 : 0, a.epi); return gemm_skinny(a, st); }     // (any product of at most 512 rows: planned split or not)
     if (a.ksplit > 1) {
         if (a.nb1 < 1 || a.nb2 != 1 || a.epi != 0 || !a.partial || a.ldc_n != 1 || a.Kp % (a.ksplit * KPAD) != 0)
             return fail(CTI_E_UNSUPPORTED, "gemm_nt_planes: split-K needs one fp32 row-major GEMM (ksplit=%d Kp=%d epi=%d)", a.ksplit, a.Kp, a.epi);
@@ -822,6 +822,7 @@ int gemm_nt_planes(const PlaneGemmArgs& a, hipStream_t st) {
         b.scale = nullptr; b.bias = nullptr; b.relu = 0;
         b.kc2 = a.Kp / a.ksplit / 16;
         int rc = gemm_nt_planes(b, st); if (rc) return rc;
+        note_gemm_route_split_k();
         if (a.partials_only) return CTI_OK;                   // the caller's own kernel reduces them (cti_linear_residual_pb)
         const int64_t items = (int64_t)a.nb1 * a.M * ((a.N + 3) / 4);
         hipLaunchKernelGGL(ksplit_reduce_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, a.partial, a.ksplit, a.M, a.N, a.C,
@@ -862,10 +863,11 @@ int gemm_nt_planes(const PlaneGemmArgs& a, hipStream_t st) {
     // CTI_GEMM16_SMALL=0: this file's kernel for them, A/B)
     static const bool small16 = [] { const char* e = getenv("CTI_GEMM16_SMALL"); return !(e && e[0] == '0'); }();
     if (a.Abf) {                                                     // a row-major bf16 A operand exists on cti_gemm16.hip only, whatever the tile and the A/B switches
-        if (!gemm16_eligible(a)) return fail(CTI_E_UNSUPPORTED, "gemm_nt_planes: a bf16-row A operand needs a product cti_gemm16.hip takes (terms=%d epi=%d Kp=%d)", a.terms, a.epi, a.Kp);
+        if (!gemm16_eligible(a, cfg)) return fail(CTI_E_UNSUPPORTED, "gemm_nt_planes: a bf16-row A operand needs a product cti_gemm16.hip takes (terms=%d epi=%d Kp=%d)", a.terms, a.epi, a.Kp);
         return gemm16_planes(a, st, cfg);
     }
-    if (use16 && (cfg == 2 || small16) && gemm16_eligible(a)) return gemm16_planes(a, st, cfg);
+    if (use16 && (cfg == 2 || small16) && gemm16_eligible(a, cfg)) return gemm16_planes(a, st, cfg);
+    note_gemm_route(GEMM_ROUTE_PLANES, cfg, a.Af ? 2 : 0, a.epi);
     const int epi = (a.epi == 3 && p.gdiv == 2 && a.ldc_n == 2) ? 2 : a.epi;
     const int key = (a.terms == 3 ? 4 : 0) + epi;
     switch (key) {

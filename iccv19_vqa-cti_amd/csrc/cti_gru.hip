@@ -610,7 +610,8 @@ static int gru_forward_impl(const float* x, const void* x16, int64_t ldx16, cons
         if (x16) {
             g.Abf = x16; g.ldabf = ldx16; g.rows_allocA = (int64_t)B * T;
             g.M = B * T; g.N = H3; g.Kp = KpI; g.terms = terms; g.epi = 0; g.C = gi; g.ldc_m = H3; g.ldc_n = 1; g.scale_div = 1; g.bias = b_ih;
-            if (!gemm16_eligible(g)) {                              // (a shape cti_gemm16.hip refuses, e.g. K < 128 with a bias: the rows through planes after all)
+            if (!gemm16_eligible(g)) {                              // (a shape cti_gemm16.hip refuses, e.g. K < 256 with a bias -- fewer stages than the deepest ring has slots: the rows through planes after all.
+                                                                    // The tile is not known here, hence the strictest rule; the extra split launch at I = 128 .. 224 was not measured: the models' I is 512 and more)
                 g.Abf = nullptr; g.ldabf = 0; g.rows_allocA = rx;
                 rc = split_planes16(static_cast<const unsigned short*>(x16), ldx16, (int64_t)B * T, KpI, xh, nullptr, rx, st); if (rc) return rc;
             }

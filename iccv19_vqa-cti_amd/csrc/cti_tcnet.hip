@@ -419,6 +419,8 @@ static int tcnet_forward_impl(const float* v, const float* q, const float* a, co
                     t.Abf = v_tucked; t.ldabf = ld_vt; t.rows_allocA = rows[0] / v_rep; t.rows_allocB = p.wr[0].rows_alloc; t.nb1 = 1; t.nb2 = 1;
                     t.M = (int)(rows[0] / v_rep); t.N = h; t.Kp = planes_kp(h); t.terms = 1; t.scale = p.scale_r[0]; t.scale_div = hr; t.bias = rank_b[0]; t.relu = relu;
                     t.epi = 0; t.C = p.Vr; t.ldc_m = h; t.ldc_n = 1;
+                    // (the tile is not known yet: the strictest rule.  With bias / scale and h = 128 .. 224 the rows then go through split_planes16 even where the
+                    // 256 x 256 tile, whose 4 stages would do, gets picked -- one launch more, not measured: the models' h is 512 and more)
                     rows_direct = planes_kp(h) == h && gemm16_eligible(t);
                 }
                 if (rows_direct) { r.Abf = v_tucked; r.ldabf = ld_vt; r.rows_allocA = rows[0] / v_rep; }

@@ -94,14 +94,14 @@ class GraphedForward:
 
     Under capture nobody can wait for the guard's verdict, so a guarded call that leaves the format's domain NaN-fills its output (range bits, heavy
     cancellation) or -- mild cancellation estimate, bit 8 -- keeps an f16f6 result whose error is still ~<= 1e-4 (ops.set_range_check).  This wrapper reads
-    the status word the replay left on the device (4 bytes into pinned host memory behind the replay, an event instead of a device-wide synchronise) and,
-    when ANY bit is set, runs `fn` again EAGERLY on the same inputs with the whole package in the mode the verdict asks for ('fp32' on bit 16, else
+    the status words the replay left on the device (one per guarded call of the captured forward, 4 bytes each into pinned host memory behind the replay, an
+    event instead of a device-wide synchronise) and, when ANY bit of ANY of them is set, runs `fn` again EAGERLY on the same inputs with the whole package in the mode the verdict asks for ('fp32' on bit 16, else
     'bf16x3'), returning that result: what the 'sync' mode of the eager path does, one replay late.
 
         g = cti_amd.GraphedForward(lambda v, q, a: model(v, q, a), (v, q, a))
         out = g(v, q, a)          # tensors of the captured graph (overwritten by the next call) or, after a trip, of the eager re-run
 
-    fn must be inference code (torch.no_grad is entered here).  `reruns` counts the trips, `last_status` is the last status word."""
+    fn must be inference code (torch.no_grad is entered here).  `reruns` counts the trips, `last_status` is the OR of the last replay's status words."""
 
     def __init__(self, fn, example_inputs, warmup=2):
         self.fn = fn
@@ -111,19 +111,25 @@ class GraphedForward:
         s = torch.cuda.Stream(device=dev)
         s.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(s), torch.no_grad():
-            for _ in range(warmup):                      # eager, on the capture stream: allocator, caches, stream-K workspaces, the guard's status block
+            # the guard's status block must exist BEFORE the capture (memory born under capture belongs to the graph's pool), and the warm-up does not create it:
+            # under the 'sync' range check its guarded calls are waited for by the host and leave nothing there
+            blk = ops._ensure_guard_block(dev)
+            for _ in range(warmup):                      # eager, on the capture stream: allocator, caches, stream-K workspaces
                 self.fn(*self.static_in)
             torch.cuda.synchronize(dev)
             self.graph = torch.cuda.CUDAGraph()
-            copies = ops._guard_block_copies[0]
-            with torch.cuda.graph(self.graph, stream=s):
-                self.static_out = self.fn(*self.static_in)
-            guarded = ops._guard_block_copies[0] > copies
+            self._nslots = 0
+            ops._guard_capture_begin(dev)
+            try:
+                with torch.cuda.graph(self.graph, stream=s):
+                    self.static_out = self.fn(*self.static_in)
+            finally:
+                self._nslots = ops._guard_capture_end(dev)   # guarded calls in the graph: each leaves its status word in a slot of its own
         torch.cuda.current_stream(dev).wait_stream(s)
         # (only a graph that holds a guarded call rewrites the status block: after a replay of any other forward -- the BAN / SAN models, a mode other than
         # f16f6 -- the block still holds what the process's LAST guarded call left there, which says nothing about this replay)
-        self._blk = ops._guard_status_block.get(dev.index if dev.index is not None else torch.cuda.current_device()) if guarded else None
-        self._host = torch.zeros(1, dtype=torch.int32).pin_memory() if self._blk is not None else None
+        self._blk = blk if self._nslots > 0 else None
+        self._host = torch.zeros(self._nslots, dtype=torch.int32).pin_memory() if self._blk is not None else None
         self._ev = torch.cuda.Event()
 
     def __call__(self, *inputs):
@@ -132,10 +138,12 @@ class GraphedForward:
         self.graph.replay()
         if self._blk is None:                            # nothing guarded was captured
             return self.static_out
-        self._host.copy_(self._blk[:4].view(torch.int32), non_blocking=True)
+        self._host.copy_(self._blk[256:256 + 4 * self._nslots].view(torch.int32), non_blocking=True)
         self._ev.record()
         self._ev.synchronize()
-        self.last_status = int(self._host[0]) & 0xffffffff
+        self.last_status = 0
+        for w in self._host.tolist():                    # ANY guarded call of the forward: the OR of their status words
+            self.last_status |= int(w) & 0xffffffff
         if not self.last_status:
             return self.static_out
         self.reruns += 1

@@ -89,26 +89,61 @@ def set_cancel_thresholds(bf16x3=2.75, fp32=5.5):
     L.check(lib.cti_set_tuning(L.TUNE_GUARD_RHO_FP32, int(round(float(fp32) * 1000))), "cti_set_tuning")
 
 
-# The guard block (first 256 B of a guarded call's workspace) of the LAST guarded call per device, copied stream-ordered into a small tensor that lives as long
-# as the process (a reference to the workspace itself pinned GBs and kept the caching allocator from recycling the block).  Under graph capture the
-# copy is a node of the graph, so after a replay the tensor holds what THAT replay found.
+# The guard block (first 256 B of a guarded call's workspace) of the LAST guarded call nobody waited for, per device, copied stream-ordered into a small tensor
+# that lives as long as the process (a reference to the workspace itself pinned GBs and kept the caching allocator from recycling the block).  Under
+# graph capture the copy is a node of the graph, so after a replay the tensor holds what THAT replay found.  Behind the 256 bytes sit GUARD_SLOTS status words,
+# one per guarded call of the capture in progress (slot = guarded calls since _guard_capture_begin): a later call's verdict must not hide an earlier one's.
+GUARD_SLOTS = 16
 _guard_status_block = {}
 _guard_block_copies = [0]          # copies issued so far: graph.GraphedForward learns from it whether the forward it captured holds a guarded call at all
+_guard_capture_slots = {}          # device -> status words written so far by the capture OPENED with _guard_capture_begin (no entry: no such capture in progress)
 
 
-def _keep_guard_block(ws):
-    key = ws.device.index if ws.device.index is not None else torch.cuda.current_device()
+def _guard_key(device):
+    return device.index if device.index is not None else torch.cuda.current_device()
+
+
+def _ensure_guard_block(device):
+    """The device's status block, created on first use.  Never under capture (memory born there belongs to that graph's pool): whoever captures calls this
+    first (graph.GraphedForward.__init__)."""
+    key = _guard_key(device)
     blk = _guard_status_block.get(key)
     if blk is None:
         if torch.cuda.is_current_stream_capturing():
-            return                        # (memory born under capture belongs to that graph's pool; an eager guarded call -- any warm-up -- creates the block)
-        blk = _guard_status_block[key] = torch.zeros(256, device=ws.device, dtype=torch.uint8)
-    blk.copy_(ws[:256], non_blocking=True)
+            raise RuntimeError("cti: the guard's status block cannot be created under graph capture -- call ops._ensure_guard_block(device) before it")
+        blk = _guard_status_block[key] = torch.zeros(256 + 4 * GUARD_SLOTS, device=device, dtype=torch.uint8)
+    return blk
+
+
+def _guard_capture_begin(device):
+    """Opens a capture whose guarded calls on `device` each leave their status word in a slot of their own, from slot 0; _guard_capture_end closes it."""
+    _ensure_guard_block(device)
+    _guard_capture_slots[_guard_key(device)] = 0
+
+
+def _guard_capture_end(device):
+    """Closes the capture opened by _guard_capture_begin: the number of status slots it wrote.  From here on captured guarded calls write the 256-byte copy only,
+    as a capture nobody opened this way always does."""
+    return _guard_capture_slots.pop(_guard_key(device), 0)
+
+
+def _keep_guard_block(ws):
+    if _guard_status_block.get(_guard_key(ws.device)) is None and torch.cuda.is_current_stream_capturing():
+        return                            # a bare capture that nobody prepared: no block to write to (the NaN fill is that caller's only signal)
+    blk = _ensure_guard_block(ws.device)
+    blk[:256].copy_(ws[:256], non_blocking=True)
+    key = _guard_key(ws.device)
+    n = _guard_capture_slots.get(key)
+    if n is not None and torch.cuda.is_current_stream_capturing():       # (a bare torch.cuda.graph capture reads no slots: it gets no slot node and never runs out of them)
+        if n >= GUARD_SLOTS:
+            raise RuntimeError("cti: more than %d guarded f16f6 calls in one captured forward (ops.GUARD_SLOTS)" % GUARD_SLOTS)
+        blk[256 + 4 * n:260 + 4 * n].copy_(ws[:4], non_blocking=True)
+        _guard_capture_slots[key] = n + 1
     _guard_block_copies[0] += 1
 
 
 def f16f6_device_status(device=None, sync=True):
-    """Status word (and rho) of the LAST guarded f16f6 call on `device`, read from the copy of its guard block -- the way to learn what a replayed hipGraph's
+    """Status word (and rho) of the LAST guarded f16f6 call on `device` that nobody waited for ('poison' mode, graph capture / replay), read from the copy of its guard block -- the way to learn what a replayed hipGraph's
     forward found.  sync=False: the caller has already waited for the stream the call ran on.  None when no guarded call has run."""
     key = torch.cuda.current_device() if device is None else (device.index if isinstance(device, torch.device) and device.index is not None else
                                                               (device if isinstance(device, int) else torch.cuda.current_device()))
@@ -120,6 +155,20 @@ def f16f6_device_status(device=None, sync=True):
     w = blk[:128].cpu().view(torch.int32)
     f = lambda i: float(w[i:i + 1].view(torch.float32)[0])
     return {"status": int(w[0]) & 0xffffffff, "rho": f(2), "abs_max": f(16), "dot_max": f(17)}
+
+
+def last_gemm_route():
+    """Which kernel the calling thread's last plane GEMM launched (tests; include/cti_hip.h, CTI_TUNE_LAST_GEMM_ROUTE and CTI_TUNE_GEMM16_LAUNCHES): a dict of kernel ('gemm16', 'planes',
+    'skinny'), cfg (the tile: 0 = 128 x 128, 1 = 256 x 128, 2 = 256 x 256; None for the skinny kernel), a_form ('planes', 'bf16_rows', 'fp32_rows'), epi
+    ('f32', 'planes', 'bf16', ...), split_k (the launch wrote split-K partials; the reduce kernel applied scale / bias / ReLU) and gemm16_launches (how many of the
+    thread's plane GEMMs went to cti_gemm16.hip so far: the difference across a fused forward counts them).  None before the first one."""
+    w = int(L.lib().cti_get_tuning(L.TUNE_LAST_GEMM_ROUTE))
+    if w <= 0:
+        return None
+    cfg = (w >> 4) & 15
+    return {"kernel": {1: "gemm16", 2: "planes", 3: "skinny"}[w & 15], "cfg": None if cfg == 15 else cfg,
+            "a_form": ("planes", "bf16_rows", "fp32_rows")[(w >> 8) & 15], "epi": {0: "f32", 1: "planes", 2: "interleaved2", 3: "interleaved", 4: "f16f6", 5: "bf16"}[(w >> 12) & 15],
+            "split_k": bool((w >> 16) & 1), "gemm16_launches": int(L.lib().cti_get_tuning(L.TUNE_GEMM16_LAUNCHES))}
 
 
 def f16f6_range_status():

@@ -72,7 +72,16 @@ enum { CTI_TUNE_GEMM_CFG = 1, CTI_TUNE_TRI_CHUNK = 2, CTI_TUNE_GUARD_RHO_BF16X3 
                                       launch needs every one of its workgroups resident: the caller must not let two of them share the device (same stream, or
                                       ordered by events); a workgroup that waits beyond CTI_GRU_PERSISTENT_SPINS polls (default 400 000) NaN-fills its outputs
                                       instead of hanging.  2 = one launch per step with the LDS-ring step kernel of rounds 3-5 (the persistent form's bit-exact reference: same
-                                      accumulation order).  Default 0: one launch per step, K split over the workgroup's waves (round 6) */ };
+                                      accumulation order).  Default 0: one launch per step, K split over the workgroup's waves (round 6) */,
+       CTI_TUNE_LAST_GEMM_ROUTE = 10 /* READ-ONLY (cti_set_tuning refuses it; tests): which kernel the calling thread's last plane GEMM (cti_gemm_nt / cti_gemm_nt_pb in a
+                                      bf16 mode, cti_gemm_bf16_rows*, or the last one inside a fused forward) launched, packed as
+                                      kernel | cfg << 4 | a_form << 8 | epi << 12 | split_k << 16:  kernel 1 = cti_gemm16.hip, 2 = the planes kernel of
+                                      cti_gemm_bf16x3.hip, 3 = cti_gemm_skinny.hip (0 = no plane GEMM yet on this thread);  cfg = the tile as in CTI_TUNE_GEMM_CFG
+                                      (15 = the skinny kernel's own);  a_form 0 = A read from planes, 1 = from bf16 rows, 2 = from fp32 rows;  epi 0 = fp32 rows,
+                                      1 = planes, 5 = bf16 rows (3 / 4: the interleaved and f16f6 outputs);  split_k = 1: that launch wrote the partials of a
+                                      split-K and scale / bias / ReLU were applied by the reduce kernel behind it */,
+       CTI_TUNE_GEMM16_LAUNCHES = 11 /* READ-ONLY (tests): how many plane GEMMs of the calling thread have gone to cti_gemm16.hip so far (mod 2^32) -- the difference across a
+                                      fused forward counts its launches of that kernel */ };
 int cti_set_tuning(int key, int64_t value);
 int64_t cti_get_tuning(int key);
 

@@ -52,6 +52,24 @@ def test_tuning_rejects_bad_values_and_defaults_to_auto():
     assert lib.cti_get_tuning(1) == -1 and lib.cti_get_tuning(2) == 0
 
 
+def test_the_gemm_route_word_is_read_only_and_per_thread():
+    """key 10 (CTI_TUNE_LAST_GEMM_ROUTE): which kernel the thread's last plane GEMM launched; key 11 (CTI_TUNE_GEMM16_LAUNCHES): how many went to cti_gemm16.hip.  A thread that has launched none reads 0 (ops.last_gemm_route(): None);
+    the key cannot be set."""
+    import threading
+    lib = L.lib()
+    assert lib.cti_set_tuning(L.TUNE_LAST_GEMM_ROUTE, 1) == -4 and b"read-only" in lib.cti_last_error_string()
+    assert lib.cti_set_tuning(L.TUNE_GEMM16_LAUNCHES, 1) == -4 and b"read-only" in lib.cti_last_error_string()
+    seen = {}
+
+    def fresh():
+        seen["word"] = lib.cti_get_tuning(L.TUNE_LAST_GEMM_ROUTE)
+        seen["route"] = cti_amd.ops.last_gemm_route()
+        seen["gemm16"] = lib.cti_get_tuning(L.TUNE_GEMM16_LAUNCHES)
+
+    t = threading.Thread(target=fresh); t.start(); t.join()
+    assert seen == {"word": 0, "route": None, "gemm16": 0}
+
+
 def test_tuning_overrides_are_thread_local():
     """include/cti_hip.h promises no process-wide mutable state: an override set on one thread is invisible to every other thread."""
     import threading

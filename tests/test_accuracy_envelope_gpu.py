@@ -238,6 +238,77 @@ def test_graph_replay_with_the_safety_net(eps, bits):
     assert (g.last_status & 7) and g.reruns == before + 1 and bool(torch.isfinite(out).all()) and err < TOL, (g.last_status, err)
 
 
+@pytest.mark.parametrize("eps,bits", [(1.0, 0), (0.35, 8), (0.13, 24)])
+def test_graph_safety_net_in_a_fresh_process(eps, bits):
+    """The same three rows, each ALONE in a child process, so that GraphedForward is the first thing in the process to meet the guard, under the default
+    'sync' range check: its warm-up forwards are waited for by the host and leave no status block behind, and a block cannot be born under capture -- the
+    wrapper has to create it itself, or every replay comes back with last_status 0 and the NaN / ~1e-4 output of the bare graph (in this file's order the
+    poison-mode test above creates the block first, which hid that).  Children run one after another; the node id selects the row (no -k: its
+    expression parser trips over the dots, and would collect this launcher again)."""
+    import os, subprocess, sys
+    node = "%s::test_graph_replay_with_the_safety_net[%s-%d]" % (os.path.abspath(__file__), eps, bits)
+    r = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", node], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=900)
+    assert r.returncode == 0 and "1 passed" in r.stdout, r.stdout[-3000:]
+
+
+@pytest.mark.parametrize("first_cancels", [True, False])
+def test_graph_with_two_guarded_calls_reports_the_first(first_cancels):
+    """One captured forward with TWO guarded f16f6 calls, one of them built to cancel heavily (eps 0.13: bits 8 + 16, NaN-filled by the replay), the other
+    untouched: every guarded call of the capture leaves its status word in a slot of its own and the wrapper ORs them, so the verdict of the FIRST call
+    survives the second one's clean word (and the other way round); the eager re-run brings both outputs back within tolerance of their own float64 oracle."""
+    sd_c, v, q, a = _case()
+    _cancelling(sd_c, 0.13)
+    sd_p, _, _, _ = _case()
+    sds = (sd_c, sd_p) if first_cancels else (sd_p, sd_c)
+    nets = [_module(sd) for sd in sds]
+    refs = [O.tcnet_forward(v, q, a, sd, dtype=np.float64) for sd in sds]
+    tv, tq, ta = T(v), T(q), T(a)
+    g = cti_amd.GraphedForward(lambda x, y, z: (nets[0](x, y, z), nets[1](x, y, z)), (tv, tq, ta))
+    for rep in range(3):
+        outs = g(tv, tq, ta)
+        errs = [float(np.max(np.abs(o.cpu().numpy() - r)) / np.max(np.abs(r))) for o, r in zip(outs, refs)]
+        print("two guarded calls (first cancels: %s), replay %d: status %d, %d re-runs, errs %.2e %.2e" % (first_cancels, rep, g.last_status, g.reruns, errs[0], errs[1]))
+        assert g.reruns == rep + 1 and (g.last_status & 24) == 24, (rep, g.reruns, g.last_status)
+        assert max(errs) < TOL, errs
+    assert (ops.f16f6_device_status()["status"] & 24) == (0 if first_cancels else 24)      # (f16f6_device_status() keeps returning the LAST call's word)
+
+
+def test_bare_captures_after_a_graphed_forward_take_no_status_slots():
+    """The status slots belong to the capture GraphedForward opens and closes: a bare torch.cuda.graph capture of a guarded forward (tests/test_range_guard_gpu.py,
+    bench.py) writes the 256-byte copy only, as it always did -- so any number of them can follow a GraphedForward in one process (twenty here, more than
+    ops.GUARD_SLOTS), each replay leaves its own verdict where f16f6_device_status() reads it, and the GraphedForward captured first still reports its own."""
+    sd, v, q, a = _case()
+    m = _module(sd)
+    tv, tq, ta = T(v), T(q), T(a)
+    g = cti_amd.GraphedForward(lambda x, y, z: m(x, y, z), (tv, tq, ta))
+    clean = g(tv, tq, ta).clone()
+    assert g.last_status == 0 and g.reruns == 0 and g._nslots == 1
+    assert not ops._guard_capture_slots                         # closed with the capture
+    big = T(a * np.float32(1e6))                               # beyond the f16 range: saturation bit, NaN fill
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s), torch.no_grad():
+        m(tv, tq, ta)                                           # eager warm-up on the capture stream
+    torch.cuda.synchronize()
+    for i in range(ops.GUARD_SLOTS + 4):
+        gr = torch.cuda.CUDAGraph()
+        xa = ta.clone()
+        with torch.cuda.stream(s), torch.no_grad():
+            with torch.cuda.graph(gr, stream=s):
+                o = m(tv, tq, xa)
+        torch.cuda.current_stream().wait_stream(s)
+        gr.replay()
+        assert ops.f16f6_device_status()["status"] == 0 and torch.equal(o, clean), i
+        xa.copy_(big)
+        gr.replay()
+        assert (ops.f16f6_device_status()["status"] & 7) and bool(torch.isnan(o).all()), i
+    assert not ops._guard_capture_slots
+    out = g(tv, tq, ta)
+    assert g.last_status == 0 and g.reruns == 0 and torch.equal(out, clean)
+    out = g(tv, tq, big)
+    assert (g.last_status & 7) and g.reruns == 1 and bool(torch.isfinite(out).all())
+
+
 @pytest.mark.parametrize("eps,expect", [(1.0, 0), (0.7, 0), (0.45, 8), (0.35, 8), (0.2, 24), (0.05, 24), (0.004, 24)])
 def test_cancelling_contraction_trips_the_estimate_and_is_rerun(eps, expect):
     """(b) the rank nets' LAST layer of the answer side built so that A^ is (nearly) orthogonal to every row of M: columns come in equal pairs and
