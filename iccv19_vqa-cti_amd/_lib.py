@@ -39,6 +39,7 @@ SIGNATURES = {
     "cti_triattention_forward_vt16": (_int, [_vp] * 13 + [_int] * 12 + [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _i64, _int]),
     "cti_triattention_hoist_ok": (_int, [_int] * 8),
     "cti_tcnet_forward_guard_bytes": (_sz, [_int] * 11),
+    "cti_tcnet_forward_plan_offset": (_sz, [_int] * 11),
     "cti_guard_read": (_int, [_vp, _vp, _vp, C.POINTER(C.c_uint32)]),
     "cti_guard_read_ratio": (_int, [_vp, _vp, C.POINTER(C.c_float)]),
     "cti_masked_softmax_tri_from_partials_fwd": (_int, [_vp, _vp, _vp, _sz, _vp, _int, _int, _i64, _int, _vp, _sz, _vp]),
@@ -161,6 +162,7 @@ E_UNSUPPORTED = -4                                   # CTI_E_UNSUPPORTED: shape 
 ACT_NONE, ACT_RELU = 0, 1
 TUNE_GEMM_CFG, TUNE_TRI_CHUNK = 1, 2                # cti_set_tuning keys
 TUNE_GUARD_RHO_BF16X3, TUNE_GUARD_RHO_FP32, TUNE_GUARD_POISON_BITS, TUNE_F6_CORE_FREE_CUS, TUNE_GUARD_STRATA, TUNE_GEMM16_SK, TUNE_GRU_PERSISTENT = 3, 4, 5, 6, 7, 8, 9     # f16f6 guard policy (include/cti_hip.h)
+TUNE_MODE3_SKIP_PADDED = 12                        # 0 = the f16f6 mode-3 product computes every tile; -1 / 1 = it skips the row tiles of zero-padded objects (filled by copy)
 TUNE_LAST_GEMM_ROUTE, TUNE_GEMM16_LAUNCHES = 10, 11    # read-only: which kernel the thread's last plane GEMM launched (ops.last_gemm_route() unpacks it); how many went to cti_gemm16.hip
 GUARD_SATURATED, GUARD_UNDERFLOW, GUARD_NONFINITE = 1, 2, 4     # status bits of the f16f6 range guard (cti_guard_read)
 

@@ -28,6 +28,7 @@ static thread_local int g_guard_strata = 1;                       // test knob: 
 static thread_local int g_gemm16_sk = -1;                          // stream-K cut of the plain-bf16 row GEMM: -1 = where it was measured to pay (three or more rounds of tiles), 0 = never, 1 = wherever it can be planned
 static thread_local int g_gru_persistent = 0;                      // 1 = cti_gru_forward may run all steps of an eligible call as ONE persistent launch (the caller keeps two of them off the chip at once)
 static thread_local int g_f6_core_free_cus = -1;                  // CUs the mode-3 product leaves to the guard kernels beside it (-1 = the library's default)
+static thread_local int g_mode3_skip = -1;                         // key 12: -1 / 1 = the f16f6 mode-3 product skips the row tiles of zero-padded objects (filled by copy), 0 = every tile
 static thread_local int g_gemm_route = 0;                         // key 10: the last plane GEMM's route (0 = none yet)
 int tuning_gemm_cfg() { return g_gemm_cfg; }
 static thread_local unsigned g_gemm16_launches = 0;                // key 11: ... and how many of them went to cti_gemm16.hip
@@ -44,6 +45,7 @@ int tuning_f6_core_free_cus() { return g_f6_core_free_cus; }
 int tuning_guard_strata() { return g_guard_strata; }
 int tuning_gemm16_sk() { return g_gemm16_sk; }
 int tuning_gru_persistent() { return g_gru_persistent; }
+int tuning_mode3_skip() { return g_mode3_skip; }
 
 }  // namespace cti
 
@@ -77,6 +79,9 @@ extern "C" int cti_set_tuning(int key, int64_t value) {
         case CTI_TUNE_GRU_PERSISTENT:
             CTI_REQUIRE(value >= 0 && value <= 2, CTI_E_SHAPE, "cti_set_tuning: GRU_PERSISTENT must be 0, 1 or 2, got %lld", (long long)value);
             g_gru_persistent = (int)value; return CTI_OK;
+        case CTI_TUNE_MODE3_SKIP_PADDED:
+            CTI_REQUIRE(value >= -1 && value <= 1, CTI_E_SHAPE, "cti_set_tuning: MODE3_SKIP_PADDED must be -1 (default: on), 0 or 1, got %lld", (long long)value);
+            g_mode3_skip = (int)value; return CTI_OK;
         case CTI_TUNE_LAST_GEMM_ROUTE:
         case CTI_TUNE_GEMM16_LAUNCHES: return fail(CTI_E_UNSUPPORTED, "cti_set_tuning: key %d is read-only", key);
         default: return fail(CTI_E_UNSUPPORTED, "cti_set_tuning: unknown key %d", key);
@@ -95,6 +100,7 @@ extern "C" int64_t cti_get_tuning(int key) {
         case CTI_TUNE_GRU_PERSISTENT: return g_gru_persistent;
         case CTI_TUNE_LAST_GEMM_ROUTE: return last_gemm_route();
         case CTI_TUNE_GEMM16_LAUNCHES: return (int64_t)g_gemm16_launches;
+        case CTI_TUNE_MODE3_SKIP_PADDED: return g_mode3_skip;
         default: return INT64_MIN;
     }
 }

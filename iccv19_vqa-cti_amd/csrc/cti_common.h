@@ -24,6 +24,7 @@ unsigned tuning_guard_poison_bits();  // key 5: status bits that NaN-fill the ou
 int tuning_guard_strata();            // key 7 (tests): 0 = the cancellation estimate without its strata maxima
 int tuning_gru_persistent();          // key 9: 1 = cti_gru_forward may use its persistent form (cti_gru.hip)
 int tuning_gemm16_sk();               // key 8: stream-K cut of cti_gemm16.hip's row products (-1 auto, 0 never, 1 wherever plannable)
+int tuning_mode3_skip();               // key 12: 0 = the f16f6 mode-3 product walks every tile; -1 / 1 = it skips the row tiles of zero-padded objects (cti_mode3_plan.hip)
 int tuning_f6_core_free_cus();        // key 6: CUs the mode-3 product leaves free for the guard kernels beside it (-1 = default)
 // key 10 (read-only; the layout is in include/cti_hip.h): which kernel this thread's last plane GEMM launched.  kernel: 1 = cti_gemm16.hip, 2 = the planes kernel of
 // cti_gemm_bf16x3.hip, 3 = cti_gemm_skinny.hip; a_form: 0 planes, 1 bf16 rows, 2 fp32 rows.  One thread-local store per call (and key 11's count of the cti_gemm16.hip ones).

@@ -122,7 +122,23 @@ struct F6GemmArgs {
     // one row's block, so the encoder runs in registers and the tile stream never pauses for LDS (cti_gemm_f16f6.hip).  The bias enters as
     // the accumulators' initial value; a weight-norm scale belongs in the weight planes (quantize_f16f6's row_scale).  nb = 1.
     const F6Planes* out;
+    // epi 3 with gdiv = 2, ldc_n = 2 and no softmax partials only, optional: the tile plan of cti_mode3_plan.hip (device memory).  The kernel then walks the plan's
+    // live tiles only -- their number is the plan's first word, read on the device -- instead of all nb x row tiles x column tiles.
+    const unsigned* plan;
 };
+// ---- tile plan of the mode-3 product (cti_mode3_plan.hip).  The output rows of two objects of a sample with identical feature rows are identical, and the
+// zero-padded objects that close a sample are exactly that: the product computes the row tiles that hold the sample's live objects and ONE padded object
+// (the representative, object n_rep = the first of the trailing run of all-zero objects), and a periodic copy fills the rest of out[b] from the
+// representative's block.  Words:  [M3P_W_*] head | per live row tile j (at most nb x row tiles) {sample, its first live row tile, its live row tiles, n_rep}
+// | per sample {first live row tile, live row tiles, n_rep, 0}.
+constexpr int M3P_HEAD_WORDS = 8, M3P_W_TILES = 0, M3P_W_ROW_TILES = 1, M3P_W_FILLED_ROWS = 2, M3P_W_SAMPLES = 3;
+inline size_t mode3_plan_bytes(int64_t nb, int tiles_m) { return sizeof(unsigned) * (size_t)(M3P_HEAD_WORDS + 4 * nb * tiles_m + 4 * nb); }
+int f6_mode3_tile_rows();                      // BM of the geometry gemm_nt_f16f6 launches the mode-3 product with
+int f6_mode3_tile_cols();
+// mask: (nb, V) bytes, 1 = all-zero object.  rows_per_obj GEMM rows per object, M = V * rows_per_obj, row tiles of bm rows, tiles_n column tiles
+int mode3_plan(const uint8_t* mask, unsigned* plan, int nb, int V, int rows_per_obj, int bm, int tiles_n, hipStream_t st);
+// out[b]: sample_floats floats, an object's block obj_floats, a row tile's rows tile_floats; fills [live row tiles x tile_floats, sample_floats) of every sample
+int mode3_fill(const unsigned* plan, int tiles_m, float* out, int nb, int64_t sample_floats, int64_t obj_floats, int64_t tile_floats, hipStream_t st);
 // ---- range guard (cti_f16f6_guard.hip): the guard block is GUARD_WORDS uint32 at the head of cti_tcnet_forward's workspace
 constexpr int GUARD_WORDS = 64, GUARD_W_STATUS = 0, GUARD_W_DONE = 1, GUARD_W_RATIO = 2, GUARD_W_SEG = 4, GUARD_MAX_SEG = 12;
 constexpr int GUARD_W_ABSMAX = 16, GUARD_W_DOTMAX = 17;      // guard_cancel: float bits of the largest sum_k |m_k a_k| / the largest |sum_k m_k a_k| over ALL batches' sampled pairs

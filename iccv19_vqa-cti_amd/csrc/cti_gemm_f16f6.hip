@@ -150,11 +150,28 @@ struct F6P {
     const float* scale; int scale_div; const float* bias; int relu;
     float* sm_part; const uint8_t* sm_mask; int sm_rows_per_obj, sm_objs; unsigned sm_magic;      // row / rows_per_obj = umulhi(row, magic) (rows < 2^24)
     char* oH; char* oFL; char* oS; int64_t o_ra, o_ras; int o_rdiv, o_rstride;                    // F6_EPI_PLANES_T: the output planes
+    const unsigned* plan;                      // F6_EPI_INTERLEAVE2, optional: the tile plan (cti_mode3_plan.hip): which tiles this launch walks
 };
 // the kernels' only parameter, as it sits at the head of the kernel-argument segment (constant address space: scalar loads)
 typedef const __attribute__((address_space(4))) F6P F6P_K;
 __device__ __forceinline__ const F6P_K* f6_kernarg() { return __builtin_bit_cast(const F6P_K*, __builtin_amdgcn_kernarg_segment_ptr()); }
 enum { F6_EPI_F32 = 0, F6_EPI_INTERLEAVE2 = 2, F6_EPI_INTERLEAVE = 3, F6_EPI_INTERLEAVE2_SM = 5, F6_EPI_PLANES_T = 6 };   // _SM: + softmax partials; _T: see F6GemmArgs
+
+// ---- tile walk from a plan (cti_f16f6.h, "tile plan"): virtual tile `id` of `total` live ones -> (sample, row tile, column tile).  As tile_coords has it, each XCD
+// walks a contiguous chunk of the virtual sequence; a sample's LIVE row tiles run fastest, so that one column tile of the B operand serves them back to back out of
+// one L2.  A sample's tiles are tiles_n x (its live row tiles) consecutive ids, so id / tiles_n is a row-tile index of that sample: ONE 16-B scalar load of that
+// entry gives the sample, its first row tile and its count.  The plan was written by an earlier kernel and is constant here (constant address space: scalar loads,
+// no vmcnt).
+typedef unsigned f6p_u32x4 __attribute__((ext_vector_type(4)));
+typedef const __attribute__((address_space(4))) f6p_u32x4 F6PlanEntry_K;
+typedef const __attribute__((address_space(4))) unsigned F6PlanWord_K;
+__device__ __forceinline__ void plan_coords(const unsigned* plan, int id, int total, int tiles_n, int& z, int& tm, int& tn) {
+    const int q = total >> 3, r = total & 7, xcd = id & 7, slot = id >> 3;
+    const int vid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;
+    const f6p_u32x4 e = __builtin_bit_cast(F6PlanEntry_K*, plan + M3P_HEAD_WORDS)[vid / tiles_n];
+    const int t = vid - (int)e[1] * tiles_n, live = (int)e[2];
+    z = (int)e[0]; tn = t / live; tm = t - tn * live;
+}
 
 template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
@@ -402,12 +419,21 @@ __global__ __launch_bounds__(G::NTHR, G::MINW) void gemm_f16f6_kernel(F6P p) {
     const int wm = wid / WN, wn = wid % WN;
     const int r = lane & 31, h = lane >> 5;
     const int tiles_n = (p.N + BN - 1) / BN, tiles_m = (p.M + BM - 1) / BM;
-    if ((int)blockIdx.x >= p.total_tiles) return;
+    // F6_EPI_INTERLEAVE2 with a tile plan: the number of tiles is the plan's first word -- what the device found live in THIS call's inputs -- and the two per-tile
+    // set-ups below map a tile index through the plan.  The plan's pointer is re-read from the kernel-argument segment where it is needed, like their other operands.
+    int total_tiles = p.total_tiles;
+    if (EPI == F6_EPI_INTERLEAVE2) {
+        const F6P_K* q = f6_kernarg();
+        asm volatile("" : "+s"(q));
+        const unsigned* plan = q->plan;
+        if (plan) total_tiles = (int)__builtin_bit_cast(F6PlanWord_K*, plan)[M3P_W_TILES];
+    }
+    if ((int)blockIdx.x >= total_tiles) return;
     // The workgroup's tiles (blockIdx.x, + gridDim.x, ...) are ONE stream of K blocks through the ring: the DMA of the next tile's first
     // blocks is issued during the current tile's last ones, so that the ring never drains at a tile boundary and the epilogue's stores
     // overlap with loads already in flight.
     const int nkb = p.Kb;
-    const int nblk = ((p.total_tiles - 1 - (int)blockIdx.x) / (int)gridDim.x + 1) * nkb;
+    const int nblk = ((total_tiles - 1 - (int)blockIdx.x) / (int)gridDim.x + 1) * nkb;
     // ---- DMA side.  Piece g = wid + 8 u (u = 0 .. 4) of the slot's list [A_H x16 | B_H x12 | A_FL x6 | B_FL x4 | B_FL tail + A_S | B_S]; the
     // last but one (wave 6, u = 4) takes its lower 32 lanes from the B_FL tail and its upper 32 from the A scales.  Every piece has a per-lane
     // 64-bit source pointer (H pieces: rows (lane >> 2) of the piece, 16-B chunk (lane & 3) ^ ((row >> 2) & 3); the others 16 B per lane) that
@@ -437,7 +463,9 @@ __global__ __launch_bounds__(G::NTHR, G::MINW) void gemm_f16f6_kernel(F6P p) {
         const F6P_K* q = f6_kernarg();
         asm volatile("" : "+s"(q));
         int zz, tm, tn;
-        tile_coords(iss_tile, p.total_tiles, tiles_m, tiles_n, zz, tm, tn);
+        const unsigned* plan = EPI == F6_EPI_INTERLEAVE2 ? q->plan : nullptr;
+        if (EPI == F6_EPI_INTERLEAVE2 && plan) plan_coords(plan, iss_tile, total_tiles, tiles_n, zz, tm, tn);
+        else tile_coords(iss_tile, total_tiles, tiles_m, tiles_n, zz, tm, tn);
         const int64_t ra = (int64_t)zz * q->rA + tm * BM, rb = (int64_t)zz * q->rB + tn * BN;
         int w = wid;
         asm volatile("" : "+s"(w));                                 // (keeps the descriptor arithmetic below out of the K loop's live registers)
@@ -468,7 +496,7 @@ __global__ __launch_bounds__(G::NTHR, G::MINW) void gemm_f16f6_kernel(F6P p) {
         ++issued;
         if (++iss_kb == nkb) {
             iss_kb = 0; iss_tile += (int)gridDim.x;
-            if (iss_tile < p.total_tiles) issue_tile_setup();
+            if (iss_tile < total_tiles) issue_tile_setup();
         }
     };
     // vmcnt part of "block b has landed": the pieces this wave issued for the blocks after b may still be in flight -- min(NST - 2, blocks
@@ -502,7 +530,13 @@ __global__ __launch_bounds__(G::NTHR, G::MINW) void gemm_f16f6_kernel(F6P p) {
     int vtile = blockIdx.x, z = 0, m0 = 0, n0 = 0;
     auto compute_tile_setup = [&]() {
         int tm, tn;
-        tile_coords(vtile, p.total_tiles, tiles_m, tiles_n, z, tm, tn);
+        if (EPI == F6_EPI_INTERLEAVE2) {
+            const F6P_K* q = f6_kernarg();
+            asm volatile("" : "+s"(q));
+            const unsigned* plan = q->plan;
+            if (plan) plan_coords(plan, vtile, total_tiles, tiles_n, z, tm, tn);
+            else tile_coords(vtile, total_tiles, tiles_m, tiles_n, z, tm, tn);
+        } else tile_coords(vtile, total_tiles, tiles_m, tiles_n, z, tm, tn);
         m0 = tm * BM; n0 = tn * BN;
     };
     compute_tile_setup();
@@ -757,6 +791,19 @@ int quantize_f16f6(const float* x, int64_t ld, int64_t rows, int K, const F6Plan
     return launch_status("quantize_f16f6");
 }
 
+int f6_mode3_tile_rows() {
+#ifdef CTI_F6_WITH_HALF_GEO
+    if (f6_geo() == 1) return GeoF6Half::BM;
+#endif
+    return GeoF6::BM;
+}
+int f6_mode3_tile_cols() {
+#ifdef CTI_F6_WITH_HALF_GEO
+    if (f6_geo() == 1) return GeoF6Half::BN;
+#endif
+    return GeoF6::BN;
+}
+
 int f6_sm_chunks(int M, int N) { return ((M + GeoF6::BM - 1) / GeoF6::BM) * ((N + GeoF6::BN - 1) / GeoF6::BN) * GeoF6::NW; }
 
 int gemm_nt_f16f6(const F6GemmArgs& a, hipStream_t st) {
@@ -778,6 +825,8 @@ int gemm_nt_f16f6(const F6GemmArgs& a, hipStream_t st) {
         case 3:
             if (a.sm_part && (a.M >= (1 << 24) || a.sm_rows_per_obj >= 256)) return fail(CTI_E_SHAPE, "gemm_nt_f16f6: softmax partials need M < 2^24 and rows per object < 256");
             if (a.sm_part && !(p.gdiv == 2 && a.ldc_n == 2 && a.sm_mask)) return fail(CTI_E_UNSUPPORTED, "gemm_nt_f16f6: softmax partials need gdiv = 2, ldc_n = 2 and a mask");
+            if (a.plan && (a.sm_part || p.gdiv != 2 || a.ldc_n != 2)) return fail(CTI_E_UNSUPPORTED, "gemm_nt_f16f6: a tile plan needs gdiv = 2, ldc_n = 2 and no softmax partials");
+            p.plan = a.plan;
             if (p.gdiv == 2 && a.ldc_n == 2) return a.sm_part ? launch_f6<F6_EPI_INTERLEAVE2_SM>(p, a.nb, a.N, st) : launch_f6<F6_EPI_INTERLEAVE2>(p, a.nb, a.N, st);
             return launch_f6<F6_EPI_INTERLEAVE>(p, a.nb, a.N, st);
         case 6:

@@ -92,6 +92,9 @@ struct Plan {
     // ... and the a-side Tucker projection: `a` is encoded once (f_Ain) and multiplied with the Tucker weight's block f_wta (scale folded in; prepared)
     // in the same transposed form
     F6Planes f_Ain, f_wta;
+    // f16f6 mode, glimpse 2, A >= 7: the mode-3 product's tile plan (cti_mode3_plan.hip) and -- for callers that pass no zero_mask -- the all-zero-object mask it is
+    // built from.  Both are written in every call that reads them.
+    uint8_t* m3_mask; unsigned* m3_plan; size_t m3_plan_off; int m3_tiles_m, m3_tiles_n;
     unsigned* guard;                           // f16f6 kernels in use: the range-guard block (GUARD_WORDS uint32) at the HEAD of the per-call workspace
     size_t bytes;
 };
@@ -159,6 +162,14 @@ Plan carve(const Dims& d, int prec, void* ws) {
             p.f_Arp = f6_carve(w.take(f6_planes_bytes(rows[2], d.h, d.A)), rows[2], d.h, d.A);
             p.Mf32 = direct_m(d) ? nullptr : static_cast<float*>(w.take(sizeof(float) * mrows * d.h));
             p.f_Mp = f6_carve(w.take(f6_planes_bytes(mrows, d.h, mpb)), mrows, d.h, mpb);
+            if (d.G == 2 && (int64_t)d.Q * d.A * d.G < (1ll << 30)) {      // (the interleaved-pairs instantiation of the product; the fill's 32-bit object offsets)
+                p.m3_tiles_m = (int)((mpb + f6_mode3_tile_rows() - 1) / f6_mode3_tile_rows());
+                p.m3_tiles_n = (d.A + f6_mode3_tile_cols() - 1) / f6_mode3_tile_cols();
+                p.m3_mask = static_cast<uint8_t*>(w.take((size_t)d.B * d.V));
+                const size_t pb = mode3_plan_bytes(d.B, p.m3_tiles_m);
+                p.m3_plan = static_cast<unsigned*>(w.take(pb));
+                p.m3_plan_off = w.off - pb;
+            }
         }
     }
     p.bytes = (w.off + 255) & ~(size_t)255;
@@ -252,6 +263,12 @@ extern "C" size_t cti_tcnet_forward_guard_bytes(int B, int V, int Q, int A, int 
     if (B <= 0 || V <= 0 || Q <= 0 || A <= 0 || v_dim <= 0 || q_dim <= 0 || a_dim <= 0 || h <= 0 || R <= 0 || G <= 0 || h % R || prec != CTI_PREC_F16F6 || h % 32) return 0;
     Dims d{B, V, Q, A, v_dim, q_dim, a_dim, h, R, G};
     return small_a(d) ? 0 : sizeof(unsigned) * GUARD_WORDS;
+}
+
+extern "C" size_t cti_tcnet_forward_plan_offset(int B, int V, int Q, int A, int v_dim, int q_dim, int a_dim, int h, int R, int G, int prec) {
+    if (B <= 0 || V <= 0 || Q <= 0 || A <= 0 || v_dim <= 0 || q_dim <= 0 || a_dim <= 0 || h <= 0 || R <= 0 || G <= 0 || h % R || prec != CTI_PREC_F16F6 || h % 32) return 0;
+    Dims d{B, V, Q, A, v_dim, q_dim, a_dim, h, R, G};
+    return carve(d, prec, nullptr).m3_plan_off;
 }
 
 // CTI_F6_GUARD_ABLATE=1 (measurement only): the guard's scan / estimate / poison kernels are not launched (the block is still reset, so the host reads
@@ -400,6 +417,19 @@ static int tcnet_forward_impl(const float* v, const float* q, const float* a, co
         if (ev_guard) (void)hipEventDestroy(ev_guard);
         return code;
     };
+    // Tile plan of the mode-3 product (f16f6, the plain forward): the mask of all-zero objects -- the caller's when it asked for one: computed above, in front of
+    // the fork -- and the one-workgroup plan kernel open chain B (the auxiliary stream's when there is one); the product and the fill behind it read the plan on
+    // the device.  Measured (profiles/r07_mode3_skip_padded.txt): in the f16f6 step chain B is not short -- its M build crawls beside the a side's rank product and
+    // ends ~0.16 ms after it -- and with nothing to skip the two launches cost the step 0.03 ms.  CTI_M3_PLAN_MAIN=1 (experiment) launches them at the head of the
+    // main stream's chain instead, behind the fork.
+    static const bool m3_plan_main = [] { const char* e = getenv("CTI_M3_PLAN_MAIN"); return e && e[0] == '1'; }();
+    const bool m3_skip = p.m3_plan && !sm_part && !order1_env && tuning_mode3_skip() != 0;
+    if (m3_skip) {
+        hipStream_t sp = m3_plan_main ? st : sb;
+        const uint8_t* mk = zero_mask;
+        if (!mk) { rc = cti_zero_row_mask(v, v_dim, p.m3_mask, rows[0], v_dim, sp); if (rc) return finish(rc); mk = p.m3_mask; }
+        rc = mode3_plan(mk, p.m3_plan, B, V, Q * G, f6_mode3_tile_rows(), p.m3_tiles_n, sp); if (rc) return finish(rc);
+    }
     const int Kh = planes_kp(h);
     // v_tucked (cti_triattention_forward, few-answer path only): v's Tucker projection was computed by the caller -- hoisted into the batched GEMM of
     // the glimpses' pooling networks and, with v_rep > 1, once per IMAGE instead of once per row (the MC pipeline repeats every image per candidate
@@ -671,8 +701,11 @@ static int tcnet_forward_impl(const float* v, const float* q, const float* a, co
             rc = guard_scan(ga, st); if (rc) return finish(rc);
             if (aux_stream) { (void)hipEventRecord(ev_guard, st); (void)hipStreamWaitEvent(sb, ev_guard, 0); }   // the verdict is visible on the auxiliary stream too (cti_hip.h)
         }
+        if (m3_skip) c.plan = p.m3_plan;
         if (ev_core_begin) (void)hipEventRecord(static_cast<hipEvent_t>(ev_core_begin), st);
         rc = gemm_nt_f16f6(c, st);
+        // the rows of the skipped tiles: copies of the representative padded object's rows, which the product has just written
+        if (!rc && m3_skip) rc = mode3_fill(p.m3_plan, p.m3_tiles_m, out, B, (int64_t)V * Q * A * G, (int64_t)Q * A * G, (int64_t)f6_mode3_tile_rows() / G * A * G, st);
         if (ev_core_end) (void)hipEventRecord(static_cast<hipEvent_t>(ev_core_end), st);
         if (rc) return finish(rc);
         if (guard_on && guard_beside) (void)hipStreamWaitEvent(st, ev_guard, 0);

@@ -238,10 +238,11 @@ class tuning:
     """Context manager over cti_set_tuning (tests / benchmarks only): `with ops.tuning(gemm_cfg=2, tri_chunk=64): ...` forces the plane GEMM's
     tile geometry (0 = 128x128, 1 = 256x128, 2 = 256x256) and / or the Tri softmax's chunk length, so small tensors run the instantiations that
     BASELINE configs[1] selects; gemm16_sk = 1 cuts every plannable product of cti_gemm_bf16_rows_sk stream-K (default: only where it pays).  Restores the
-    previous values on exit."""
+    previous values on exit.  mode3_skip_padded = 0: the f16f6 mode-3 product computes every tile (default: the row tiles of zero-padded objects are filled by
+    copy; same output bit for bit)."""
 
-    def __init__(self, gemm_cfg=None, tri_chunk=None, gemm16_sk=None):
-        self.want = {L.TUNE_GEMM_CFG: gemm_cfg, L.TUNE_TRI_CHUNK: tri_chunk, L.TUNE_GEMM16_SK: gemm16_sk}
+    def __init__(self, gemm_cfg=None, tri_chunk=None, gemm16_sk=None, mode3_skip_padded=None):
+        self.want = {L.TUNE_GEMM_CFG: gemm_cfg, L.TUNE_TRI_CHUNK: tri_chunk, L.TUNE_GEMM16_SK: gemm16_sk, L.TUNE_MODE3_SKIP_PADDED: mode3_skip_padded}
 
     def __enter__(self):
         lib = L.lib()
@@ -636,6 +637,23 @@ def tcnet_prepare(tucker, rank, T_g, prec=None):
     return block, pr
 
 
+_debug_keep_mode3_plan = False   # tests / diagnostics: keep a view of the last fused forward's mode-3 tile plan (it holds that call's whole workspace until the next call)
+_last_mode3_plan = [None]  # that view, or None where the call built no plan
+
+
+def last_mode3_plan():
+    """With ops._debug_keep_mode3_plan set: totals of the tile plan the calling process's last tcnet_forward built (include/cti_hip.h, "Tile plan"): a dict of live_tiles (tiles the mode-3 product walked),
+    live_row_tiles, filled_rows (rows of the (V Q G) x A product written by the fill kernel) and samples -- or None when that call built no plan (another mode or
+    shape, the softmax-partials form, or the key CTI_TUNE_MODE3_SKIP_PADDED at 0).  Synchronises (tests and diagnostics)."""
+    t = _last_mode3_plan[0]
+    if t is None:
+        return None
+    w = t.cpu().view(torch.int32).tolist()
+    if w[3] == 0:                               # the head as tcnet_forward zeroed it: the library built no plan in that call
+        return None
+    return {"live_tiles": w[0], "live_row_tiles": w[1], "filled_rows": w[2], "samples": w[3]}
+
+
 _debug_ws_fill = None      # tests only: byte value the fused forward's workspace is filled with before the call
 
 
@@ -702,6 +720,13 @@ def tcnet_forward(v, q, a, tucker, rank, T_g, relu=True, want_mask=False, prec=N
     ws = torch.empty(wsb, device=v.device, dtype=torch.uint8)
     if _debug_ws_fill is not None:              # tests: the library must not read workspace bytes it has not written (0xFF reads as saturated scale bytes)
         ws.fill_(_debug_ws_fill)
+    _last_mode3_plan[0] = None
+    if _debug_keep_mode3_plan and pr == L.PREC_F16F6:
+        # the library says whether it built a plan: the head is zeroed here, in front of the call, and a call that builds one writes it (word 3 = B)
+        po = lib.cti_tcnet_forward_plan_offset(B, V, Q, A, vd, qd, ad, h, R, G, pr)
+        if po:
+            _last_mode3_plan[0] = ws[po:po + 16]
+            _last_mode3_plan[0].zero_()
     ev0 = ev1 = None
     if _prof is not None:                       # hipEvents around the mode-3 GEMM, recorded by the library on the launch stream
         ev0, ev1 = lib.cti_event_create(), lib.cti_event_create()

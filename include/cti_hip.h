@@ -81,7 +81,11 @@ enum { CTI_TUNE_GEMM_CFG = 1, CTI_TUNE_TRI_CHUNK = 2, CTI_TUNE_GUARD_RHO_BF16X3 
                                       1 = planes, 5 = bf16 rows (3 / 4: the interleaved and f16f6 outputs);  split_k = 1: that launch wrote the partials of a
                                       split-K and scale / bias / ReLU were applied by the reduce kernel behind it */,
        CTI_TUNE_GEMM16_LAUNCHES = 11 /* READ-ONLY (tests): how many plane GEMMs of the calling thread have gone to cti_gemm16.hip so far (mod 2^32) -- the difference across a
-                                      fused forward counts its launches of that kernel */ };
+                                      fused forward counts its launches of that kernel */,
+       CTI_TUNE_MODE3_SKIP_PADDED = 12 /* cti_tcnet_forward, CTI_PREC_F16F6, glimpse 2, more than 6 answer tokens: -1 / 1 (default) = the mode-3 product computes, per
+                                      sample, the row tiles up to and including ONE of the all-zero objects that close the sample (the padding of the collate
+                                      function: all of them give bit-identical output rows) and a copy kernel fills the remaining rows of out[b] from that
+                                      object's rows; 0 = every tile is computed (the A/B and the tests' reference).  Same output, bit for bit.  See "Tile plan" below */ };
 int cti_set_tuning(int key, int64_t value);
 int64_t cti_get_tuning(int key);
 
@@ -217,6 +221,13 @@ size_t cti_tcnet_softmax_partials_bytes(int B, int V, int Q, int A, int h, int G
 enum { CTI_GUARD_SATURATED = 1, CTI_GUARD_UNDERFLOW = 2, CTI_GUARD_NONFINITE = 4, CTI_GUARD_CANCEL = 8, CTI_GUARD_CANCEL_HEAVY = 16 };
 int cti_guard_read_ratio(const void* workspace, void* stream, float* ratio_host);
 size_t cti_tcnet_forward_guard_bytes(int B, int V, int Q, int A, int v_dim, int q_dim, int a_dim, int h, int R, int G, int prec);
+/* Tile plan of the f16f6 mode-3 product (CTI_TUNE_MODE3_SKIP_PADDED).  Every call builds it on the device from the all-zero-object mask of `v` (the caller's
+ * zero_mask, or B * V bytes of the workspace), on aux_stream when there is one, without a host read: the call stays capturable and a replay follows the `v` it
+ * finds.  cti_tcnet_forward_workspace_bytes includes the mask and the plan (16 B per sample and per row tile of a sample + 32 B).
+ * cti_tcnet_forward_plan_offset: byte offset of the plan's head in `workspace` (0 = this shape / mode builds none): uint32 words [0] tiles the product walked,
+ * [1] row tiles (of 256 rows of the (V Q G) x A product per sample) among them, [2] rows of that product filled by copy, [3] B -- valid once the call's work on
+ * `stream` has completed, and only after a call that ran with the key on (diagnostics and tests). */
+size_t cti_tcnet_forward_plan_offset(int B, int V, int Q, int A, int v_dim, int q_dim, int a_dim, int h, int R, int G, int prec);
 int cti_guard_read(const void* workspace, void* event, void* stream, uint32_t* status_host);
 /* The batch-independent part of cti_tcnet_forward, computed once per parameter update: the six weight-norm scales, T_eff (and its
  * [r][(j,k,g)][i] copy), and in the bf16 modes the hi/lo operand planes of the six weight matrices.  `prepared`: a device block of
