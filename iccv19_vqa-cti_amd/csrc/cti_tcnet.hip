@@ -419,13 +419,13 @@ static int tcnet_forward_impl(const float* v, const float* q, const float* a, co
     };
     // Tile plan of the mode-3 product (f16f6, the plain forward): the mask of all-zero objects -- the caller's when it asked for one: computed above, in front of
     // the fork -- and the one-workgroup plan kernel open chain B (the auxiliary stream's when there is one); the product and the fill behind it read the plan on
-    // the device.  Measured (profiles/r07_mode3_skip_padded.txt): in the f16f6 step chain B is not short -- its M build crawls beside the a side's rank product and
-    // ends ~0.16 ms after it -- and with nothing to skip the two launches cost the step 0.03 ms.  CTI_M3_PLAN_MAIN=1 (experiment) launches them at the head of the
-    // main stream's chain instead, behind the fork.
-    static const bool m3_plan_main = [] { const char* e = getenv("CTI_M3_PLAN_MAIN"); return e && e[0] == '1'; }();
+    // the device.  Measured (profiles/r07_mode3_skip_padded.txt, r08_mode3_fill.txt): in the f16f6 step chain B is not short -- its M build crawls beside the a side's
+    // rank product and ends ~0.16 ms after it -- and with nothing to skip the two launches cost the step 0.02-0.03 ms.  The other placement, both launches at the
+    // head of the main stream's chain behind the fork, was measured against this one (r08, section 3): 4.068 against 4.057 ms per step on the benchmark's inputs,
+    // +0.04 against +0.02-0.03 ms with nothing to skip -- no better anywhere, so they stay here.
     const bool m3_skip = p.m3_plan && !sm_part && !order1_env && tuning_mode3_skip() != 0;
     if (m3_skip) {
-        hipStream_t sp = m3_plan_main ? st : sb;
+        hipStream_t sp = sb;
         const uint8_t* mk = zero_mask;
         if (!mk) { rc = cti_zero_row_mask(v, v_dim, p.m3_mask, rows[0], v_dim, sp); if (rc) return finish(rc); mk = p.m3_mask; }
         rc = mode3_plan(mk, p.m3_plan, B, V, Q * G, f6_mode3_tile_rows(), p.m3_tiles_n, sp); if (rc) return finish(rc);
