@@ -21,9 +21,11 @@ from .teacher_logits import make_json_with_logits, dump_teacher_logits, load_tea
 from . import base_model                                       # noqa: F401
 from .base_model import BanModel, CTIModel, TanModel, MCBanModel, build_ban, build_cti, build_mc_cti, build_mc_ban   # noqa: F401
 from .base_model import StackedAttentionModel, MCStackedAttentionModel, build_san, build_mc_san   # noqa: F401
+from .score import compute_score_with_logits, compute_score_mc, ScoreMeter, evaluate, evaluate_mc   # noqa: F401
 
 __all__ = ["FCNet", "WNLinear", "TCNet", "BCNet", "BiAttention", "TriAttention", "StackedAttention", "Counter", "PiecewiseLin", "ModeProduct",
            "ops", "set_precision", "get_precision", "invalidate_caches", "set_range_check", "f16f6_range_status", "CtiError", "FlatAdamaxDP", "GraphedTrainStep", "GraphedForward",
            "WordEmbedding", "QuestionEmbedding", "SimpleClassifier", "BCEWithLogitsSum", "Distillation_Loss", "base_model",
            "BanModel", "CTIModel", "TanModel", "MCBanModel", "build_ban", "build_cti", "build_mc_cti", "build_mc_ban",
-           "StackedAttentionModel", "MCStackedAttentionModel", "build_san", "build_mc_san"]
+           "StackedAttentionModel", "MCStackedAttentionModel", "build_san", "build_mc_san",
+           "compute_score_with_logits", "compute_score_mc", "ScoreMeter", "evaluate", "evaluate_mc"]

@@ -155,7 +155,12 @@ SIGNATURES = {
     "cti_counter_save_bytes": (_sz, [_i64]),
     "cti_counter_fwd": (_int, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _int, _vp, _i64, _i64, _vp, _sz, _int, _int, _int, _int, _int, _int, _vp]),
     "cti_counter_bwd": (_int, [_vp, _vp, _i64, _i64, _i64, _vp, _int, _vp, _sz, _vp, _vp, _int, _int, _int, _int, _int, _int, _vp]),
+    "cti_score_rows": (_int, [_vp, _vp, _i64, _int, _vp, _vp, _vp, _vp, _vp]),
+    "cti_score_mc": (_int, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),
+    "cti_meter_add_scores": (_int, [_vp, _vp, _i64, _vp, _i64, _i64, _vp]),
+    "cti_meter_add_scalar": (_int, [_vp, _int, _vp, _vp]),
 }
+METER_SCORE, METER_UPPER, METER_LOSS, METER_GRAD_NORM, METER_BYTES = 0, 1, 2, 3, 64     # the meter block of cti_meter_add_* (include/cti_hip.h)
 
 PREC_F32, PREC_BF16X3, PREC_BF16, PREC_F16F6 = 0, 1, 2, 3
 E_UNSUPPORTED = -4                                   # CTI_E_UNSUPPORTED: shape / mode outside a specialised kernel

@@ -2159,3 +2159,77 @@ def kd_rows_bwd(x, knowledge, upstream, coef, T, dx=None, beta=0.0):
     L.check(L.lib().cti_kd_rows_bwd(xc.data_ptr(), kc.data_ptr(), _ptr(upstream), float(coef), dx.data_ptr(), xc.numel() // n, n, float(T),
                                     float(beta), _stream()), "cti_kd_rows_bwd")
     return dx
+
+
+# ---- answer scoring and the device-side meter (include/cti_hip.h: cti_score_rows / cti_score_mc / cti_meter_add_*; score.py is the public face) ----
+def _score_pair(logits, labels, what):
+    _req(logits, "logits"); _req(labels, "labels")
+    if logits.dim() != 2 or labels.dim() != 2 or logits.shape[0] != labels.shape[0]:
+        raise ValueError("%s: logits %s and labels %s must be 2-D with the same number of rows" % (what, tuple(logits.shape), tuple(labels.shape)))
+    return logits if logits.is_contiguous() else logits.contiguous()
+
+
+def score_rows(logits, labels, dense=False):
+    """The FFOE rule (src/FFOE/trainer.py:296-303) in ONE launch: logits, labels (rows, n) fp32 -> (pred (rows,) int64 = torch.max(logits, 1)[1] with the
+    CPU's tie / NaN semantics, score (rows,) = labels[r, pred[r]], upper (rows,) = labels.max(1)[0]); dense=True appends the reference's (rows, n)
+    `one_hots * labels`.  No synchronisation, no torch kernel."""
+    logits = _score_pair(logits, labels, "score_rows")
+    if logits.shape != labels.shape:
+        raise ValueError("score_rows: logits %s, labels %s" % (tuple(logits.shape), tuple(labels.shape)))
+    if not labels.is_contiguous():
+        labels = labels.contiguous()
+    rows, n = logits.shape
+    if n == 0:
+        raise ValueError("score_rows: rows of no answers have no arg-max")
+    dev = logits.device
+    pred = torch.empty(rows, device=dev, dtype=torch.int64)
+    score = torch.empty(rows, device=dev, dtype=torch.float32)
+    upper = torch.empty(rows, device=dev, dtype=torch.float32)
+    out = torch.empty(rows, n, device=dev, dtype=torch.float32) if dense else None
+    if rows:
+        L.check(L.lib().cti_score_rows(logits.data_ptr(), labels.data_ptr(), rows, n, pred.data_ptr(), score.data_ptr(), upper.data_ptr(), _ptr(out),
+                                       _stream()), "cti_score_rows")
+    return (pred, score, upper, out) if dense else (pred, score, upper)
+
+
+def score_mc(logits, labels):
+    """The MC rule (src/MC/trainer.py:292-300) in ONE launch: logits (rows, 2), labels (rows, >= 1) of which column 0 is read -> (pred (rows // 4,) int64: per
+    group of four rows the row whose fp32 class-0 softmax probability is the first maximum, score (rows // 4,) = labels[pred, 0], upper (rows,) =
+    labels[:, 0]).  The rows % 4 trailing rows belong to no group and appear in `upper` only."""
+    logits = _score_pair(logits, labels, "score_mc")
+    if logits.shape[1] != 2 or labels.shape[1] < 1:
+        raise ValueError("score_mc: logits %s must be (rows, 2) and labels %s (rows, >= 1)" % (tuple(logits.shape), tuple(labels.shape)))
+    if labels.stride(0) < 1:                             # (an expanded column; any positive row stride is read as it stands)
+        labels = labels.contiguous()
+    rows = logits.shape[0]
+    dev = logits.device
+    pred = torch.empty(rows // 4, device=dev, dtype=torch.int64)
+    score = torch.empty(rows // 4, device=dev, dtype=torch.float32)
+    upper = torch.empty(rows, device=dev, dtype=torch.float32)
+    if rows:
+        L.check(L.lib().cti_score_mc(logits.data_ptr(), labels.data_ptr(), labels.stride(0), rows, pred.data_ptr(), score.data_ptr(), upper.data_ptr(),
+                                     _stream()), "cti_score_mc")
+    return pred, score, upper
+
+
+def meter_block(device):
+    """A zeroed meter block (include/cti_hip.h: four double sums, two int64 counts) as a (8,) float64 tensor."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise L.CtiError("the meter block lives on the GPU, got device %s (no CPU path)" % device)
+    return torch.zeros(L.METER_BYTES // 8, device=device, dtype=torch.float64)
+
+
+def meter_add_scores(block, score, upper, samples):
+    """block += (sum(score), sum(upper), samples): one single-workgroup launch, double sums in a fixed order (bitwise reproducible)."""
+    _req(block, "block", torch.float64); _req(score, "score"); _req(upper, "upper")
+    L.check(L.lib().cti_meter_add_scores(block.data_ptr(), score.data_ptr(), score.numel(), upper.data_ptr(), upper.numel(), int(samples), _stream()),
+            "cti_meter_add_scores")
+
+
+def meter_add_scalar(block, slot, value):
+    """block[slot] += value, a 0-dim or 1-element fp32 DEVICE tensor (never read by the host); slot METER_LOSS also counts one update."""
+    _req(block, "block", torch.float64); _req(value, "value")
+    if value.numel() != 1:
+        raise ValueError("meter_add_scalar: a 0-dim or 1-element tensor, got %s" % (tuple(value.shape),))
+    L.check(L.lib().cti_meter_add_scalar(block.data_ptr(), int(slot), value.data_ptr(), _stream()), "cti_meter_add_scalar")

@@ -744,6 +744,47 @@ int cti_counter_fwd(const float* logits, int64_t sLb, int64_t sLg, int64_t sLv, 
 int cti_counter_bwd(const float* dout, const float* boxes, int64_t sBb, int64_t sBc, int64_t sBv, const float* const* weights, int already_sigmoided,
                     const void* save, size_t save_bytes, float* dlogits, float* dw_part, int B, int G, int V, int Q, int objects, int n, void* stream);
 
+/* ---- answer scoring  (src/FFOE/trainer.py:296-303 = src/FFOE/train.py:16-21; src/MC/trainer.py:292-300 = src/MC/train.py:14-19) and the
+ * device-side meter of the training / evaluation loops (src/FFOE/train.py:83-86,142-148) ------------------------------------------------ */
+/* FFOE rule, one workgroup per row; logits, labels (rows, n) fp32, rows contiguous (row r at + r*n: any 4-byte alignment), each read once:
+ *     pred[r]  = the arg-max of logits[r,:] as torch.max(logits, 1)[1] defines it on the CPU: among equal maxima the LOWEST index; a NaN counts as
+ *                the maximum, among several NaNs the lowest index; a row of -inf gives 0; +inf ties give the lowest index          (rows) int64
+ *     score[r] = labels[r, pred[r]]                                                                                               (rows)
+ *     upper[r] = max_c labels[r, c]   (labels are finite soft scores: fmaxf, a NaN label is skipped)                              (rows)
+ *     dense[r,c] = (c == pred[r] ? 1 : 0) * labels[r,c]   -- only when dense != NULL: the reference's `one_hots * labels`          (rows, n)
+ * The arg-max is a reduction over (value, index) pairs under ONE total order at every level (lane, wave, workgroup): the larger value, NaN above
+ * every number, the lower index among equals; its identity is (-inf, INT_MAX).
+ * rows == 0 launches nothing.  CTI_E_NULL: a required pointer is NULL; CTI_E_SHAPE: rows < 0 or n <= 0.  Scratch-free, no atomics, nothing
+ * allocated or synchronised (capturable); nothing is launched on an argument error. */
+int cti_score_rows(const float* logits, const float* labels, int64_t rows, int n, int64_t* pred, float* score, float* upper, float* dense /* optional */,
+                   void* stream);
+/* MC rule: logits (rows, 2) contiguous; labels: element (r, 0) at labels + r*ld_labels (only column 0 is read).  For each group g < rows / 4 of four
+ * consecutive rows:
+ *     p0[i]    = e0 / (e0 + e1), e_k = expf(x_k - max(x_0, x_1)) of row 4g + i: the fp32 class-0 softmax probability, which saturates to exactly 1.0f
+ *                (x_0 - x_1 >= 17) and 0.0f (x_0 - x_1 < -104) as torch.softmax does -- the comparison is made on p0, so such candidates TIE
+ *     pred[g]  = 4g + the lowest i whose p0 is the group's maximum (the order of cti_score_rows: NaN above every number)       (rows / 4) int64
+ *     score[g] = labels[pred[g], 0]                                                                                            (rows / 4)
+ *     upper[r] = labels[r, 0] for EVERY row, the rows % 4 trailing ones included (they belong to no group)                      (rows)
+ * pred / score may be NULL when rows < 4.  CTI_E_NULL; CTI_E_SHAPE: rows < 0 or ld_labels < 1.  Capturable as above. */
+int cti_score_mc(const float* logits, const float* labels, int64_t ld_labels, int64_t rows, int64_t* pred, float* score, float* upper, void* stream);
+/* The meter block: CTI_METER_BYTES (64) of device memory owned (and zeroed) by the caller, 8-byte aligned:
+ *     byte  0  double  sum of scores            (CTI_METER_SCORE)
+ *           8  double  sum of upper bounds      (CTI_METER_UPPER)
+ *          16  double  sum of losses            (CTI_METER_LOSS)
+ *          24  double  sum of gradient norms    (CTI_METER_GRAD_NORM)
+ *          32  int64   samples
+ *          40  int64   updates
+ *          48  16 bytes reserved (left alone)
+ * cti_meter_add_scores: ONE workgroup sums score[0 .. n_score) and upper[0 .. n_upper) in double in a fixed order (element i belongs to thread i % 256,
+ * then a fixed tree over the threads) and adds the two sums and `samples` to the block: no floating-point atomics, two runs give bit-identical sums.
+ * cti_meter_add_scalar: block.slot += (double) value[0], value an fp32 scalar in DEVICE memory; slot CTI_METER_LOSS also counts one update.
+ * The block is updated by plain read-modify-write in stream order: one block belongs to one stream at a time.  Sizes are kernel arguments, values
+ * never are, so a captured call accumulates once per replay.  CTI_E_NULL: block, value, or an array whose count is > 0; CTI_E_ALIGN: block not 8-byte
+ * aligned; CTI_E_SHAPE: a negative count, a slot outside 0 .. 3. */
+enum { CTI_METER_SCORE = 0, CTI_METER_UPPER = 1, CTI_METER_LOSS = 2, CTI_METER_GRAD_NORM = 3, CTI_METER_BYTES = 64 };
+int cti_meter_add_scores(void* block, const float* score, int64_t n_score, const float* upper, int64_t n_upper, int64_t samples, void* stream);
+int cti_meter_add_scalar(void* block, int slot, const float* value, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
