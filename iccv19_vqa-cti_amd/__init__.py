@@ -22,10 +22,12 @@ from . import base_model                                       # noqa: F401
 from .base_model import BanModel, CTIModel, TanModel, MCBanModel, build_ban, build_cti, build_mc_cti, build_mc_ban   # noqa: F401
 from .base_model import StackedAttentionModel, MCStackedAttentionModel, build_san, build_mc_san   # noqa: F401
 from .score import compute_score_with_logits, compute_score_mc, ScoreMeter, evaluate, evaluate_mc   # noqa: F401
+from .trainer import Trainer, MCTrainer                        # noqa: F401
 
 __all__ = ["FCNet", "WNLinear", "TCNet", "BCNet", "BiAttention", "TriAttention", "StackedAttention", "Counter", "PiecewiseLin", "ModeProduct",
            "ops", "set_precision", "get_precision", "invalidate_caches", "set_range_check", "f16f6_range_status", "CtiError", "FlatAdamaxDP", "GraphedTrainStep", "GraphedForward",
            "WordEmbedding", "QuestionEmbedding", "SimpleClassifier", "BCEWithLogitsSum", "Distillation_Loss", "base_model",
            "BanModel", "CTIModel", "TanModel", "MCBanModel", "build_ban", "build_cti", "build_mc_cti", "build_mc_ban",
            "StackedAttentionModel", "MCStackedAttentionModel", "build_san", "build_mc_san",
-           "compute_score_with_logits", "compute_score_mc", "ScoreMeter", "evaluate", "evaluate_mc"]
+           "compute_score_with_logits", "compute_score_mc", "ScoreMeter", "evaluate", "evaluate_mc",
+           "Trainer", "MCTrainer"]

@@ -14,6 +14,14 @@ Two forms:
         eager  : dist.all_reduce(flat_g)                                      (the ONE collective, reference trainer.py:221-232)
         graph B: scale + norm, clip + Adamax, step / dropout counters
     = two hipGraphLaunch + one ncclAllReduce per step from the host instead of ~500 launches, so the ranks time the GPU and the xGMI, not Python.
+
+Micro-batch accumulation (the reference's --update_freq; `accumulate=True`): ALWAYS two graphs, because a micro-batch and an update are different
+amounts of work and the host decides per call which one it wants --
+        graph M: zero_grad, forward, loss, backward, FlatAdamaxDP.accumulate()  (cti_flat_gather_acc: overwrite on the first micro-batch, += after)
+        eager  : dist.all_reduce(flat_g)                                        (only with a process group; not captured, for the reason above)
+        graph U: FlatAdamaxDP.apply_accumulated()                               (scale by 1 / (world * buffered), clip + Adamax, counters, count = 0)
+The number of buffered micro-batches is a device-resident counter that both graphs read, so one capture serves every position inside an update and
+updates of any length.
 Batches are fed by copying into static input tensors."""
 import torch
 
@@ -21,12 +29,27 @@ from . import ops
 
 
 class GraphedTrainStep:
-    def __init__(self, model, optimizer, loss_fn, example_inputs, example_target, warmup=2, split_collective=None):
+    def __init__(self, model, optimizer, loss_fn, example_inputs, example_target, warmup=2, split_collective=None, accumulate=False):
         """loss_fn(model_output, target) -> scalar tensor.  example_inputs: tuple of tensors (shapes / dtypes are frozen); warmup eager steps run on
         a side stream first (allocator, one-time attributes, weight-norm caches), as torch's capture rules ask.  The warm-up steps DO update the
-        parameters.  split_collective: None = the two-graph form exactly when the optimizer issues a collective; True / False force it."""
+        parameters.  split_collective: None = the two-graph form exactly when the optimizer issues a collective; True / False force it.
+        accumulate=True: graphs M and U of the module docstring; a warm-up step is then one micro-batch + one update and needs an optimiser with
+        nothing buffered, while warmup=0 captures in whatever state the optimiser is (capturing executes nothing and leaves the buffered count alone;
+        the caller has run the step eagerly before)."""
         self.model, self.opt, self.loss_fn = model, optimizer, loss_fn
-        self.split = optimizer.needs_collective() if split_collective is None else bool(split_collective)
+        self.accumulate = bool(accumulate)
+        if self.accumulate:
+            if warmup and optimizer.micro_count:
+                raise RuntimeError("GraphedTrainStep(accumulate=True, warmup=%d): %d micro-batch(es) are buffered, the warm-up would fold them into an update"
+                                   % (warmup, optimizer.micro_count))
+            self.split = True
+        else:
+            if optimizer.update_freq != 1:
+                raise ValueError("GraphedTrainStep captures one update per replay: an optimiser with update_freq=%d would divide a single micro-batch by %d; "
+                                 "use accumulate=True" % (optimizer.update_freq, optimizer.update_freq))
+            if optimizer.micro_count:
+                raise RuntimeError("%d micro-batch(es) are buffered through accumulate(): use accumulate=True" % optimizer.micro_count)
+            self.split = optimizer.needs_collective() if split_collective is None else bool(split_collective)
         self.static_in = tuple(t.clone() for t in example_inputs)
         self.static_tgt = example_target.clone()
         self.graph = torch.cuda.CUDAGraph()
@@ -42,9 +65,20 @@ class GraphedTrainStep:
                 self._step()
         torch.cuda.synchronize()
         s = torch.cuda.Stream()
+        host = (optimizer.micro_count, optimizer.step_count)
         with torch.cuda.stream(s):
             ops.invalidate_caches()                      # the captured step must contain the per-step refresh of every derived cache
-            if not self.split:
+            if self.accumulate:
+                mode = "thread_local" if optimizer.needs_collective() else "global"
+                with torch.cuda.graph(self.graph, stream=s, capture_error_mode=mode):
+                    self.static_loss = self._forward_backward()
+                with torch.cuda.graph(self.graph_update, stream=s, capture_error_mode=mode):
+                    self.opt.apply_accumulated()
+                optimizer.micro_count, optimizer.step_count = host   # capturing executed nothing: the host mirrors go back
+                # the modules' derived caches now point at tensors of the graph's pool that no replay has filled yet, and a buffering replay does
+                # not end in a bump of the epoch: an eager micro-step (another batch shape) must not pick them up
+                ops.invalidate_caches()
+            elif not self.split:
                 with torch.cuda.graph(self.graph, stream=s):
                     self.static_loss = self._step()
             else:
@@ -59,32 +93,61 @@ class GraphedTrainStep:
         self.opt.zero_grad()
         loss = self.loss_fn(self.model(*self.static_in), self.static_tgt)
         loss.backward()
-        self.opt.gather_grads()
+        if self.accumulate:
+            self.opt.accumulate()
+        else:
+            self.opt.gather_grads()
         return loss.detach()
 
     def _step(self):
         loss = self._forward_backward()
         self.opt.all_reduce_grads()
-        self.opt.apply_update()
+        if self.accumulate:
+            self.opt.apply_accumulated()
+        else:
+            self.opt.apply_update()
         return loss
 
-    def replay(self):
+    def replay(self, update_params=True):
         """The captured step on whatever the static tensors hold.  Replays rewrite the parameters on the device behind every host-side cache key
         (weight-norm scales, operand planes of TCNet / the GRU are keyed on a package-wide epoch + storage + autograd version, none of which a
         replay moves), so the epoch is bumped here: an eager forward between two replays must not reuse planes of the older parameters.
-        Anyone replaying `.graph` directly must call ops.invalidate_caches() as well."""
+        Anyone replaying `.graph` directly must call ops.invalidate_caches() as well.  accumulate=True: update_params=False replays graph M alone."""
         self.graph.replay()
+        if self.accumulate:
+            self.opt.micro_count += 1                    # host mirror of the device-side count the replay bumped
+            if update_params:
+                self.update()
+            return
         if self.split:
             self.opt.all_reduce_grads()                  # eager: the one collective, stream-ordered between the two graphs
             self.graph_update.replay()
         ops.invalidate_caches()
 
-    def __call__(self, inputs, target):
-        """One training step on a new batch (copied into the captured tensors); returns the loss tensor of the replay (device, no sync)."""
+    def update(self):
+        """accumulate=True only: the collective and graph U alone, over whatever is buffered -- replayed micro-batches and micro-batches fed eagerly
+        through FlatAdamaxDP.accumulate() alike (an epoch's short last batch has another shape than the captured one).  Returns the optimiser's
+        grad_norm tensor (device, no sync)."""
+        if not self.accumulate:
+            raise RuntimeError("GraphedTrainStep.update() belongs to the accumulate=True form")
+        if self.opt.micro_count == 0:
+            raise RuntimeError("GraphedTrainStep.update(): no micro-batch is buffered")
+        self.opt.all_reduce_grads()                      # eager, stream-ordered between the graphs (no-op without a process group)
+        self.graph_update.replay()
+        self.opt.micro_count = 0
+        ops.invalidate_caches()
+        return self.opt.grad_norm
+
+    def __call__(self, inputs, target, update_params=True):
+        """One training step on a new batch (copied into the captured tensors); returns the loss tensor of the replay (device, no sync).
+        accumulate=True: one MICRO-batch; update_params=False buffers it (graph M only), True also applies the update over everything buffered.
+        The returned loss is this micro-batch's."""
+        if not update_params and not self.accumulate:
+            raise ValueError("update_params=False needs GraphedTrainStep(accumulate=True)")
         for dst, src in zip(self.static_in, inputs):
             dst.copy_(src, non_blocking=True)
         self.static_tgt.copy_(target, non_blocking=True)
-        self.replay()
+        self.replay(update_params)
         return self.static_loss
 
 

@@ -571,6 +571,16 @@ int cti_flat_scale_sumsq(float* grad, int64_t n, float inv_denom, float* partial
  * whose source already IS its slot is left untouched.  n: floats in flat, a multiple of 4.  The entries travel in kernel arguments
  * (160 per launch), so the host array may be reused as soon as the call returns. */
 int cti_flat_gather(const int64_t* table, int n_entries, float* flat, int64_t n, void* stream);
+/* Micro-batch accumulation (the reference's --update_freq, src/FFOE/trainer.py:112-126) with the number of buffered micro-batches in DEVICE
+ * memory, so one captured graph serves the first and every later micro-batch of an update.
+ * cti_flat_gather_acc: the table, checks and launches of cti_flat_gather; every launch reads micro_count[0].  0: exactly cti_flat_gather.
+ * > 0: flat[slot + j] += src[j] (one fp32 add per element); a slot whose source is NULL or already IS the slot, and every float outside the
+ * sources, is left as it is (the padding keeps its zeros).  The counter is not changed: bump it with cti_counter_add after the call.
+ * cti_flat_scale_sumsq_g: cti_flat_scale_sumsq with inv_denom = 1 / (world * max(micro_count[0], 1)) formed on the device.
+ * cti_counter_set: counter[0] = value in stream order (resets the micro-batch count behind the update). */
+int cti_flat_gather_acc(const int64_t* table, int n_entries, float* flat, int64_t n, const int64_t* micro_count, void* stream);
+int cti_flat_scale_sumsq_g(float* grad, int64_t n, int world, const int64_t* micro_count, float* partial, void* stream);
+int cti_counter_set(int64_t* counter, int64_t value, void* stream);
 /* norm = sqrt(sum partial); coef = min(1, max_norm / (norm + 1e-6)) (max_norm <= 0: no clipping); g' = coef * grad;
  * exp_avg = b1*exp_avg + (1-b1)*g'; exp_inf = max(b2*exp_inf, |g'| + eps); param -= lr / (1 - b1^step) * exp_avg / exp_inf.
  * grad_norm_out: NULL or one float (the pre-clip norm, for logging without a blocking .item() in the step). */
