@@ -378,8 +378,9 @@ int cti_swish_bwd(const float* x, const float* dy, float* dx, int64_t n, void* s
 }
 
 int cti_seq_sum(const float* x, float* out, int B, int L, int H, float beta, void* stream) {
-    CTI_REQUIRE_PTR(x); CTI_REQUIRE_PTR(out);
+    CTI_REQUIRE_PTR(out);
     CTI_REQUIRE(B >= 0 && L >= 0 && H > 0, CTI_E_SHAPE, "cti_seq_sum: B=%d L=%d H=%d", B, L, H);
+    if (L > 0) CTI_REQUIRE_PTR(x);                                    // an empty sequence has no storage (torch hands over NULL) and is never read: out = beta * out
     if (B == 0) return CTI_OK;
     hipLaunchKernelGGL(seq_sum_kernel, dim3(blocks_for((int64_t)B * H, 256)), dim3(256), 0, as_stream(stream), x, out, B, L, H, beta);
     return launch_status("cti_seq_sum");

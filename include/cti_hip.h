@@ -654,7 +654,7 @@ int cti_counter_add(int64_t* counter, int64_t inc, void* stream);
 int cti_swish_fwd(const float* x, float* y, int64_t n, void* stream);
 int cti_swish_bwd(const float* x, const float* dy, float* dx, int64_t n, void* stream);
 
-/* out[b,h] = beta * out[b,h] + sum_l x[b,l,h]          (q_emb.sum(1), src/FFOE/base_model.py:66,134; x (B,L,H) contiguous) */
+/* out[b,h] = beta * out[b,h] + sum_l x[b,l,h]          (q_emb.sum(1), src/FFOE/base_model.py:66,134; x (B,L,H) contiguous; L = 0: x may be NULL) */
 int cti_seq_sum(const float* x, float* out, int B, int L, int H, float beta, void* stream);
 /* out[b,l,h] = x[b,l,h] + y[b,h]  (x NULL = 0)         (q_prj(b_emb.unsqueeze(1)) + q_emb, src/FFOE/base_model.py:61,131-132) */
 int cti_seq_bcast_add(const float* x, const float* y, float* out, int B, int L, int H, void* stream);
