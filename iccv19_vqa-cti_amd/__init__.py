@@ -22,6 +22,7 @@ from . import base_model                                       # noqa: F401
 from .base_model import BanModel, CTIModel, TanModel, MCBanModel, build_ban, build_cti, build_mc_cti, build_mc_ban   # noqa: F401
 from .base_model import StackedAttentionModel, MCStackedAttentionModel, build_san, build_mc_san   # noqa: F401
 from .score import compute_score_with_logits, compute_score_mc, ScoreMeter, evaluate, evaluate_mc   # noqa: F401
+from .predict import Predictions, PredictionBuffer, predict, TypeMeter, tdiuc_summary, tdiuc_tables   # noqa: F401
 from .trainer import Trainer, MCTrainer                        # noqa: F401
 
 __all__ = ["FCNet", "WNLinear", "TCNet", "BCNet", "BiAttention", "TriAttention", "StackedAttention", "Counter", "PiecewiseLin", "ModeProduct",
@@ -30,4 +31,5 @@ __all__ = ["FCNet", "WNLinear", "TCNet", "BCNet", "BiAttention", "TriAttention",
            "BanModel", "CTIModel", "TanModel", "MCBanModel", "build_ban", "build_cti", "build_mc_cti", "build_mc_ban",
            "StackedAttentionModel", "MCStackedAttentionModel", "build_san", "build_mc_san",
            "compute_score_with_logits", "compute_score_mc", "ScoreMeter", "evaluate", "evaluate_mc",
+           "Predictions", "PredictionBuffer", "predict", "TypeMeter", "tdiuc_summary", "tdiuc_tables",
            "Trainer", "MCTrainer"]

@@ -7,44 +7,15 @@
 //   score_mc_kernel     one thread per group of 4 rows: the fp32 class-0 softmax probability of each, the first maximum of the four
 //   meter_scores_kernel ONE workgroup: the batch's scores / upper bounds summed in double in a fixed order, added to the caller's 64-byte block
 //   meter_scalar_kernel one thread: block.slot += a device-resident fp32 scalar (a loss, a gradient norm)
-// The arg-max has to reproduce torch.max(x, 1)[1] on the CPU: the lowest index among equal maxima, a NaN counts as the maximum, the lowest index
-// among several NaNs.  wave_max / block_max (fmaxf) drop NaNs and carry no index, so the reduction runs on (value, index) pairs under `beats()`,
-// a TOTAL order (value, NaN on top, then the lower index): commutative and associative, so the lane loop, the wave butterfly and the combine of
-// the four waves may visit the elements in any order and agree.  Its identity (-inf, INT_MAX) makes a row of -inf come out as index 0.
+// The arg-max has to reproduce torch.max(x, 1)[1] on the CPU (ties, NaNs): it is a reduction over (value, index) pairs under `beats()` of cti_argmax.h,
+// which cti_predict.hip shares, together with the split of a 4-byte aligned row into 16-byte loads.
 // Nothing here allocates, synchronises, uses a float atomic or takes a per-step value as an argument (capturable, bitwise reproducible).
-#include "cti_common.h"
-
-#include <limits.h>
-#include <math.h>
+#include "cti_argmax.h"
 
 namespace cti {
 namespace {
 
 constexpr int SC_THREADS = 256;
-
-// does (vb, ib) come before (va, ia) in the arg-max order?  ib != ia for distinct elements, so exactly one of beats(a, b) / beats(b, a) holds
-__device__ __forceinline__ bool beats(float vb, int ib, float va, int ia) {
-    const bool nb = vb != vb, na = va != va;
-    if (nb != na) return nb;                       // a NaN beats any number
-    if (!nb && vb != va) return vb > va;           // two numbers: the larger (-0 == +0, inf == inf: ties)
-    return ib < ia;                                // equal values, or NaN against NaN: the lower index
-}
-
-struct ArgMax {
-    float v; int i;
-    __device__ __forceinline__ void take(float x, int idx) { if (beats(x, idx, v, i)) { v = x; i = idx; } }
-};
-
-// Row r of a (rows, n) array starts 4 n r bytes into it: only 4-byte aligned in general (n = 3129).  The 16-byte loads therefore cover the aligned
-// middle [head, head + 4 * quads) of each row; the <= 3 elements in front of it and behind it are read one by one.
-struct RowSplit { int head, quads; };
-__device__ __forceinline__ RowSplit split_row(const float* row, int n) {
-    RowSplit s;
-    s.head = (int)(((16u - (unsigned)(reinterpret_cast<uintptr_t>(row) & 15u)) & 15u) >> 2);
-    if (s.head > n) s.head = n;
-    s.quads = (n - s.head) >> 2;
-    return s;
-}
 
 __global__ __launch_bounds__(SC_THREADS) void score_rows_kernel(const float* __restrict__ logits, const float* __restrict__ labels, int n,
                                                                 long long* __restrict__ pred, float* __restrict__ score, float* __restrict__ upper,

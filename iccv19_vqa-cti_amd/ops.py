@@ -2233,3 +2233,71 @@ def meter_add_scalar(block, slot, value):
     if value.numel() != 1:
         raise ValueError("meter_add_scalar: a 0-dim or 1-element tensor, got %s" % (tuple(value.shape),))
     L.check(L.lib().cti_meter_add_scalar(block.data_ptr(), int(slot), value.data_ptr(), _stream()), "cti_meter_add_scalar")
+
+
+# ---- the test pass and the TDIUC tallies (include/cti_hip.h: cti_predict_rows / cti_predict_advance / cti_type_tally; predict.py is the public face) ----
+def _cuda_device(device, what):
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise L.CtiError("%s lives on the GPU, got device %s (no CPU path)" % (what, device))
+    return device
+
+
+def predict_state(capacity, n, device):
+    """The state block of a prediction buffer (include/cti_hip.h): int64 [cursor = 0, overflow = 0, capacity, n] on the device."""
+    device = _cuda_device(device, "the prediction buffer")
+    if capacity < 0 or n < 1:
+        raise ValueError("predict_state: capacity=%r n=%r" % (capacity, n))
+    return torch.tensor([0, 0, int(capacity), int(n)], dtype=torch.int64).to(device)
+
+
+def predict_rows(logits, qid, state, answers, qids, half=None):
+    """One append: the arg-max, the question id and (half given) the float16 copy of every row of `logits` (rows, n) fp32 written at the state block's
+    cursor, then the cursor moved on by the second, one-thread launch.  Nothing is read back: an append that does not fit only sets the block's
+    overflow word.  No synchronisation, no torch kernel."""
+    _req(logits, "logits"); _req(qid, "qid", torch.int64); _req(state, "state", torch.int64)
+    _req(answers, "answers", torch.int64); _req(qids, "qids", torch.int64)
+    if half is not None:
+        _req(half, "half", torch.float16)
+    if logits.dim() != 2 or qid.dim() != 1 or qid.shape[0] != logits.shape[0]:
+        raise ValueError("predict_rows: logits %s must be (rows, n) and qid %s (rows,)" % (tuple(logits.shape), tuple(qid.shape)))
+    if state.numel() != L.PREDICT_STATE_BYTES // 8:
+        raise ValueError("predict_rows: the state block has 4 int64 words, got %d" % state.numel())
+    rows, n = logits.shape
+    if n == 0:
+        raise ValueError("predict_rows: rows of no answers have no arg-max")
+    if not logits.is_contiguous():
+        logits = logits.contiguous()
+    if not qid.is_contiguous():
+        qid = qid.contiguous()
+    if rows:
+        lib, st = L.lib(), _stream()
+        L.check(lib.cti_predict_rows(logits.data_ptr(), qid.data_ptr(), rows, n, state.data_ptr(), answers.data_ptr(), qids.data_ptr(), _ptr(half), st),
+                "cti_predict_rows")
+        L.check(lib.cti_predict_advance(state.data_ptr(), rows, st), "cti_predict_advance")
+
+
+def type_table(T, K, device):
+    """A zeroed tally block: (T, K + 1, 2) int64 cells followed by the invalid counter, as one flat int64 tensor (one copy reads both)."""
+    device = _cuda_device(device, "the type table")
+    if T < 1 or K < 1:
+        raise ValueError("type_table: T=%r K=%r" % (T, K))
+    return torch.zeros(T * (K + 1) * 2 + 1, device=device, dtype=torch.int64)
+
+
+def type_tally(block, T, K, pred, gt, qtype, lut=None):
+    """block (of type_table) += the rows' tallies: cell [qtype][gt + 1] counts the row and, when the (lut-mapped) prediction equals gt >= 0, a hit; a row
+    out of range only bumps the invalid counter.  64-bit integer atomics: any order gives identical tables.  No synchronisation."""
+    _req(block, "block", torch.int64); _req(pred, "pred", torch.int64); _req(gt, "gt", torch.int64); _req(qtype, "qtype", torch.int64)
+    if lut is not None:
+        _req(lut, "lut", torch.int64)
+    rows = pred.numel()
+    if gt.numel() != rows or qtype.numel() != rows:
+        raise ValueError("type_tally: pred, gt and qtype must have one entry per row, got %d, %d, %d" % (rows, gt.numel(), qtype.numel()))
+    cells = T * (K + 1) * 2
+    if block.numel() != cells + 1:
+        raise ValueError("type_tally: the block of T=%d, K=%d has %d words, got %d" % (T, K, cells + 1, block.numel()))
+    pred, gt, qtype = pred.contiguous(), gt.contiguous(), qtype.contiguous()
+    if rows:
+        L.check(L.lib().cti_type_tally(pred.data_ptr(), _ptr(lut), 0 if lut is None else lut.numel(), gt.data_ptr(), qtype.data_ptr(), rows, T, K,
+                                       block.data_ptr(), block.data_ptr() + 8 * cells, _stream()), "cti_type_tally")

@@ -795,6 +795,40 @@ enum { CTI_METER_SCORE = 0, CTI_METER_UPPER = 1, CTI_METER_LOSS = 2, CTI_METER_G
 int cti_meter_add_scores(void* block, const float* score, int64_t n_score, const float* upper, int64_t n_upper, int64_t samples, void* stream);
 int cti_meter_add_scalar(void* block, int slot, const float* value, void* stream);
 
+/* ---- the test pass (src/FFOE/test.py:78-130: get_logits / make_json / make_json_with_logits) and the TDIUC tallies
+ * (src/evaluate_TDIUC.py:26-94) on the device ------------------------------------------------------------------------------------------------ */
+/* The state block of a prediction buffer: CTI_PREDICT_STATE_BYTES (32) of device memory owned by the caller, 8-byte aligned, four int64:
+ *     [CTI_PREDICT_CURSOR]    rows appended so far (the caller zeroes it)
+ *     [CTI_PREDICT_OVERFLOW]  sticky: non-zero once an append did not fit (the caller zeroes it)
+ *     [CTI_PREDICT_CAPACITY]  rows the three tables below hold (set by the caller)
+ *     [CTI_PREDICT_N]         answer candidates per row (set by the caller)
+ * The tables: answers, qids (capacity) int64 and, optionally, half (capacity, n) float16, contiguous, any 2-byte alignment.
+ * cti_predict_rows: one workgroup per row of logits (rows, n) fp32, rows contiguous (any 4-byte alignment), each read once.  With c = the cursor:
+ *     answers[c + r] = the arg-max of logits[r,:] in the order of cti_score_rows (lowest index among equal maxima, a NaN on top, the lowest index
+ *                      among NaNs), taken on the fp32 values
+ *     qids[c + r]    = qid[r]
+ *     half[c + r, j] = logits[r, j] rounded to float16, only when half != NULL: round to nearest even, bit for bit numpy's astype(np.float16)
+ *                      (+-inf from 65520 upward, subnormal halves kept, -0 kept, a NaN keeps its sign and the top ten bits of its payload)
+ * If the overflow word is set, c + rows > capacity, or n differs from the block's, NO table is written and the overflow word is set.  The cursor is
+ * read, never written: cti_predict_advance (one thread, the next launch on the same stream) adds `rows` to it unless the overflow word is set.
+ * Sizes are kernel arguments, the cursor never is, so a captured append / advance pair lands behind the previous one at every replay.  One buffer
+ * belongs to one stream at a time.  rows == 0 launches nothing.  CTI_E_NULL: a required pointer is NULL; CTI_E_SHAPE: rows < 0, n <= 0;
+ * CTI_E_ALIGN: state not 8-byte or half not 2-byte aligned.  No atomics, nothing allocated or synchronised. */
+enum { CTI_PREDICT_CURSOR = 0, CTI_PREDICT_OVERFLOW = 1, CTI_PREDICT_CAPACITY = 2, CTI_PREDICT_N = 3, CTI_PREDICT_STATE_BYTES = 32 };
+int cti_predict_rows(const float* logits, const int64_t* qid, int64_t rows, int n, int64_t* state, int64_t* answers, int64_t* qids,
+                     void* half /* optional */, void* stream);
+int cti_predict_advance(int64_t* state, int64_t rows, void* stream);
+/* One thread per row: table (T, K + 1, 2) int64 and the counter invalid[0], both owned (and zeroed) by the caller, 8-byte aligned.
+ *     p = lut != NULL ? lut[pred[i]] : pred[i]      lut (n_labels) maps the model's label index to the index of that answer in the answer key; an
+ *                                                   entry < 0 = not in the key, never correct
+ *     table[qtype[i]][gt[i] + 1][0] += 1            gt = -1: the true answer is not in the key (that row of the table never gets a hit)
+ *     table[qtype[i]][gt[i] + 1][1] += 1            when gt[i] >= 0 and p == gt[i]
+ * A row with qtype outside [0, T), gt outside [-1, K), pred outside [0, n_labels) (without a lut: [0, K)) or a lut entry >= K is not tallied and adds 1 to
+ * invalid[0].  The adds are 64-bit INTEGER atomics: any order of rows and calls gives identical tables.  rows == 0 launches nothing.  CTI_E_NULL;
+ * CTI_E_SHAPE: rows < 0, T < 1, K < 1, a lut with n_labels < 1; CTI_E_ALIGN. */
+int cti_type_tally(const int64_t* pred, const int64_t* lut /* optional */, int64_t n_labels, const int64_t* gt, const int64_t* qtype, int64_t rows, int T,
+                   int K, int64_t* table, int64_t* invalid, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
