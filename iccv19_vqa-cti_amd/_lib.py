@@ -165,10 +165,16 @@ SIGNATURES = {
     "cti_predict_rows": (_int, [_vp, _vp, _i64, _int, _vp, _vp, _vp, _vp, _vp]),
     "cti_predict_advance": (_int, [_vp, _i64, _vp]),
     "cti_type_tally": (_int, [_vp, _vp, _i64, _vp, _vp, _i64, _int, _int, _vp, _vp, _vp]),
+    "cti_batch_objects": (_int, [_vp, _i64, _i64, _int, _vp, _i64, _i64, _vp, _vp, _i64, _int, _int, _vp, _vp, _vp, _vp, _vp]),
+    "cti_batch_targets": (_int, [_vp, _vp, _vp, _i64, _vp, _i64, _i64, _int, _vp, _vp, _vp]),
+    "cti_batch_rows": (_int, [_vp, _int, _vp, _i64, _i64, _int, _vp, _vp, _vp]),
 }
 METER_SCORE, METER_UPPER, METER_LOSS, METER_GRAD_NORM, METER_BYTES = 0, 1, 2, 3, 64     # the meter block of cti_meter_add_* (include/cti_hip.h)
 
 PREDICT_CURSOR, PREDICT_OVERFLOW, PREDICT_CAPACITY, PREDICT_N, PREDICT_STATE_BYTES = 0, 1, 2, 3, 32     # the state block of cti_predict_rows / cti_predict_advance
+
+BATCH_BAD_INDEX, BATCH_BAD_IMAGE, BATCH_BAD_POS, BATCH_BAD_PAD, BATCH_BAD_ANSWER, BATCH_STATE_BYTES = 0, 1, 2, 3, 4, 64     # the state block of cti_batch_*
+BATCH_I32_I64, BATCH_I64_I64, BATCH_F16_F32, BATCH_F32_F32 = 0, 1, 2, 3                                                    # cti_batch_rows modes
 
 PREC_F32, PREC_BF16X3, PREC_BF16, PREC_F16F6 = 0, 1, 2, 3
 E_UNSUPPORTED = -4                                   # CTI_E_UNSUPPORTED: shape / mode outside a specialised kernel

@@ -2301,3 +2301,98 @@ def type_tally(block, T, K, pred, gt, qtype, lut=None):
     if rows:
         L.check(L.lib().cti_type_tally(pred.data_ptr(), _ptr(lut), 0 if lut is None else lut.numel(), gt.data_ptr(), qtype.data_ptr(), rows, T, K,
                                        block.data_ptr(), block.data_ptr() + 8 * cells, _stream()), "cti_type_tally")
+
+
+# ---- a batch assembled on the device (include/cti_hip.h: cti_batch_objects / cti_batch_targets / cti_batch_rows; batch.py is the public face) ----
+_BATCH_WORDS = ("an entry index outside the data set", "an image index outside the feature table", "a pos_boxes row outside the feature table",
+                "an image with more objects than the batch is padded to", "an answer span or label outside its table")
+
+
+def batch_state(device):
+    """A zeroed state block of the cti_batch_* calls (include/cti_hip.h): (8,) int64 on the device, sticky words set to 1."""
+    return torch.zeros(L.BATCH_STATE_BYTES // 8, device=_cuda_device(device, "the batch state block"), dtype=torch.int64)
+
+
+def batch_state_errors(state):
+    """What the block's sticky words say, as a list of phrases (empty: clean).  Copies the block to the host: synchronises."""
+    host = state.cpu().tolist()
+    return [w for k, w in enumerate(_BATCH_WORDS) if host[k]]
+
+
+def _batch_idx(idx, state):
+    _req(idx, "idx", torch.int64); _req(state, "state", torch.int64)
+    if idx.dim() != 1 or not idx.is_contiguous():
+        raise ValueError("idx must be a contiguous (B,) tensor, got %s" % (tuple(idx.shape),))
+    if state.numel() != L.BATCH_STATE_BYTES // 8:
+        raise ValueError("the batch state block has 8 int64 words, got %d" % state.numel())
+    return idx.shape[0]
+
+
+def _batch_out(out, shape, dtype, device, name):
+    if out is None:
+        return torch.empty(shape, device=device, dtype=dtype)
+    _req(out, name, dtype)
+    if tuple(out.shape) != tuple(shape) or not out.is_contiguous():
+        raise ValueError("%s must be a contiguous %s tensor, got %s" % (name, tuple(shape), tuple(out.shape)))
+    return out
+
+
+def batch_objects(table, image, pos, idx, max_boxes, Vpad, state, out=None, counts=None, mask=None):
+    """out (B, Vpad, d) = for each b the first min(count, max_boxes) rows of image[idx[b]]'s block [pos[i, 0], pos[i, 1]) of `table` (rows, d) fp32 or
+    bf16, zero rows behind them; `counts` (B,) int32 and `mask` (B, Vpad) uint8 (1 = padding row) are filled when given.  One launch, no
+    synchronisation, no torch kernel; whatever is out of range becomes a zero sample and a sticky word of `state`."""
+    if not isinstance(table, torch.Tensor) or table.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError("table must be an fp32 or bf16 tensor")
+    _req(table, "table", table.dtype); _req(image, "image", torch.int64); _req(pos, "pos", torch.int64)
+    B = _batch_idx(idx, state)
+    if table.dim() != 2 or not table.is_contiguous() or pos.dim() != 2 or pos.shape[1] != 2 or not pos.is_contiguous() or image.dim() != 1 \
+            or not image.is_contiguous():
+        raise ValueError("batch_objects: table %s must be (rows, d), pos %s (n_img, 2), image %s (N,), all contiguous"
+                         % (tuple(table.shape), tuple(pos.shape), tuple(image.shape)))
+    rows, d = table.shape
+    out = _batch_out(out, (B, int(Vpad), d), table.dtype, table.device, "out")
+    if counts is not None:
+        counts = _batch_out(counts, (B,), torch.int32, table.device, "counts")
+    if mask is not None:
+        mask = _batch_out(mask, (B, int(Vpad)), torch.uint8, table.device, "mask")
+    L.check(L.lib().cti_batch_objects(table.data_ptr(), rows, d, table.element_size(), idx.data_ptr(), B, image.shape[0], image.data_ptr(), pos.data_ptr(),
+                                      pos.shape[0], int(max_boxes), int(Vpad), out.data_ptr(), _ptr(counts), _ptr(mask), state.data_ptr(), _stream()),
+            "cti_batch_objects")
+    return out
+
+
+def batch_targets(off, labels, scores, idx, n, state, out=None):
+    """out (B, n) fp32 = the reference's zeros(n).scatter_(0, labels, scores) of every entry idx[b], from the CSR triple off (N + 1,) int64, labels int32,
+    scores fp32: zeroed and scattered in one launch."""
+    _req(off, "off", torch.int64); _req(labels, "labels", torch.int32); _req(scores, "scores")
+    B = _batch_idx(idx, state)
+    if off.dim() != 1 or off.shape[0] < 2 or labels.shape != scores.shape or labels.dim() != 1:
+        raise ValueError("batch_targets: off %s must be (N + 1,), labels %s and scores %s (nnz,)" % (tuple(off.shape), tuple(labels.shape), tuple(scores.shape)))
+    out = _batch_out(out, (B, int(n)), torch.float32, off.device, "out")
+    nnz = labels.shape[0]
+    L.check(L.lib().cti_batch_targets(off.data_ptr(), labels.data_ptr() if nnz else 0, scores.data_ptr() if nnz else 0, nnz, idx.data_ptr(), B,
+                                      off.shape[0] - 1, int(n), out.data_ptr(), state.data_ptr(), _stream()), "cti_batch_targets")
+    return out
+
+
+_BATCH_ROW_MODES = {(torch.int32, torch.int64): L.BATCH_I32_I64, (torch.int64, torch.int64): L.BATCH_I64_I64,
+                    (torch.float16, torch.float32): L.BATCH_F16_F32, (torch.float32, torch.float32): L.BATCH_F32_F32}
+
+
+def batch_rows(src, idx, state, out=None):
+    """out (B, ...) = src[idx] for src (N, ...) contiguous: int32 -> int64, int64 -> int64, float16 -> fp32 (exact) or fp32 -> fp32."""
+    if not isinstance(src, torch.Tensor):
+        raise TypeError("src must be a tensor")
+    _req(src, "src", src.dtype)
+    dt = {torch.int32: torch.int64, torch.float16: torch.float32}.get(src.dtype, src.dtype)
+    if (src.dtype, dt) not in _BATCH_ROW_MODES:
+        raise TypeError("batch_rows: src must be int32, int64, float16 or float32, got %s" % src.dtype)
+    B = _batch_idx(idx, state)
+    if src.dim() < 1 or src.shape[0] < 1 or not src.is_contiguous():
+        raise ValueError("batch_rows: src %s must be a contiguous (N, ...) tensor with N >= 1" % (tuple(src.shape),))
+    w = src[0].numel()
+    out = _batch_out(out, (B,) + tuple(src.shape[1:]), dt, src.device, "out")
+    if w:
+        L.check(L.lib().cti_batch_rows(src.data_ptr(), _BATCH_ROW_MODES[(src.dtype, dt)], idx.data_ptr(), B, src.shape[0], w, out.data_ptr(),
+                                       state.data_ptr(), _stream()), "cti_batch_rows")
+    return out

@@ -829,6 +829,45 @@ int cti_predict_advance(int64_t* state, int64_t rows, void* stream);
 int cti_type_tally(const int64_t* pred, const int64_t* lut /* optional */, int64_t n_labels, const int64_t* gt, const int64_t* qtype, int64_t rows, int T,
                    int K, int64_t* table, int64_t* invalid, void* stream);
 
+/* ---- a batch assembled on the device from resident tables (src/FFOE/dataset.py:350-376 and src/MC/dataset.py:246-265: __getitem__;
+ * src/utils.py:120-169: trim_collate) ------------------------------------------------------------------------------------------------------ */
+/* All three take the batch as idx (B) int64 in DEVICE memory: entry numbers in [0, N).  They read device memory only, allocate and synchronise
+ * nothing, use no atomic and take no per-step value as an argument: a captured call replays with whatever idx holds then.  B == 0 launches nothing.
+ * The state block: CTI_BATCH_STATE_BYTES (64) of device memory owned (and zeroed) by the caller, 8-byte aligned, int64 words that are only ever set
+ * to 1 (sticky; one block may serve every call of a data set):
+ *     [CTI_BATCH_BAD_INDEX]   an idx[b] outside [0, N)
+ *     [CTI_BATCH_BAD_IMAGE]   an image[e] outside [0, n_img)
+ *     [CTI_BATCH_BAD_POS]     a pos pair with s < 0, t < s or t > table_rows
+ *     [CTI_BATCH_BAD_PAD]     a sample with more than Vpad rows after the cut to max_boxes (the first Vpad are written)
+ *     [CTI_BATCH_BAD_ANSWER]  a CSR span outside [0, nnz], or a label outside [0, n) (that label is skipped)
+ * What is out of range is never dereferenced; the sample (the row) is written as zeros.
+ *
+ * cti_batch_objects: with e = idx[b], [s, t) = pos[2 * image[e]], pos[2 * image[e] + 1], n = min(t - s, max_boxes):
+ *     out[b, 0:n, :] = table[s : s + n, :]      out[b, n:Vpad, :] = 0      counts[b] = n      mask[b, r] = r >= n
+ * table (table_rows, d) and out (B, Vpad, d) hold elements of elem_bytes = 4 (fp32) or 2 (bf16), contiguous, aligned to the element only: where a
+ * sample's source and destination agree mod 16 bytes (always, for d * elem_bytes a multiple of 16 and 16-byte aligned arrays) its block is copied by
+ * 16-byte loads and stores, otherwise through LDS with 16-byte accesses over the aligned middle of either side.  image (N) and pos (n_img, 2) are
+ * int64; counts (B) int32 and mask (B, Vpad) uint8 are optional.  One workgroup per 16 KiB of a sample's block.
+ * CTI_E_SHAPE: table_rows < 0, d < 1, elem_bytes not 2 or 4, B < 0, N < 1, n_img < 1, max_boxes < 0, Vpad < 1, more than INT_MAX workgroups. */
+enum { CTI_BATCH_BAD_INDEX = 0, CTI_BATCH_BAD_IMAGE = 1, CTI_BATCH_BAD_POS = 2, CTI_BATCH_BAD_PAD = 3, CTI_BATCH_BAD_ANSWER = 4, CTI_BATCH_STATE_BYTES = 64 };
+int cti_batch_objects(const void* table, int64_t table_rows, int64_t d, int elem_bytes, const int64_t* idx, int64_t B, int64_t N, const int64_t* image,
+                      const int64_t* pos, int64_t n_img, int max_boxes, int Vpad, void* out, int32_t* counts /* optional */, uint8_t* mask /* optional */,
+                      int64_t* state, void* stream);
+/* The reference's `target = zeros(n); target.scatter_(0, labels, scores)` from a CSR table: off (N + 1) int64, labels (nnz) int32, scores (nnz) fp32.
+ *     out[b, :] = 0      out[b, labels[k]] = scores[k] for k in [off[idx[b]], off[idx[b] + 1])
+ * in one pass per row (one workgroup per row; the row is zeroed and scattered in LDS, then stored once).  The labels of one entry must be unique (as
+ * scatter_ needs them to be for a defined result).  out (B, n) fp32 contiguous, any 4-byte alignment.  labels / scores may be NULL when nnz == 0.
+ * CTI_E_SHAPE: nnz < 0, B < 0, N < 1, n < 1. */
+int cti_batch_targets(const int64_t* off, const int32_t* labels, const float* scores, int64_t nnz, const int64_t* idx, int64_t B, int64_t N, int n, float* out,
+                      int64_t* state, void* stream);
+/* out[b, :] = src[idx[b], :] for rows of w elements, src (N, w) and out (B, w) contiguous, widened by `mode`:
+ *     CTI_BATCH_I32_I64  int32 -> int64      CTI_BATCH_I64_I64  int64 -> int64      CTI_BATCH_F32_F32  fp32 -> fp32
+ *     CTI_BATCH_F16_F32  float16 -> fp32, exact: subnormal halves and signed zeros / infinities kept, a NaN keeps its sign and its ten payload bits
+ *                        (the inverse of cti_predict_rows' rounding)
+ * One thread per element.  CTI_E_SHAPE: B < 0, N < 1, w < 1; CTI_E_UNSUPPORTED: another mode; CTI_E_ALIGN: an array not aligned to its element. */
+enum { CTI_BATCH_I32_I64 = 0, CTI_BATCH_I64_I64 = 1, CTI_BATCH_F16_F32 = 2, CTI_BATCH_F32_F32 = 3 };
+int cti_batch_rows(const void* src, int mode, const int64_t* idx, int64_t B, int64_t N, int w, void* out, int64_t* state, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
