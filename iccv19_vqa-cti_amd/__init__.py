@@ -24,7 +24,7 @@ from .base_model import StackedAttentionModel, MCStackedAttentionModel, build_sa
 from .score import compute_score_with_logits, compute_score_mc, ScoreMeter, evaluate, evaluate_mc   # noqa: F401
 from .predict import Predictions, PredictionBuffer, predict, TypeMeter, tdiuc_summary, tdiuc_tables   # noqa: F401
 from .trainer import Trainer, MCTrainer                        # noqa: F401
-from .batch import PackedDataset, pack_dataset, DeviceDataset, DeviceLoader   # noqa: F401
+from .batch import PackedDataset, pack_dataset, DeviceDataset, DeviceLoader, bucket_plan, bucket_widths_for, rank_plan   # noqa: F401
 
 __all__ = ["FCNet", "WNLinear", "TCNet", "BCNet", "BiAttention", "TriAttention", "StackedAttention", "Counter", "PiecewiseLin", "ModeProduct",
            "ops", "set_precision", "get_precision", "invalidate_caches", "set_range_check", "f16f6_range_status", "CtiError", "FlatAdamaxDP", "GraphedTrainStep", "GraphedForward",
@@ -33,4 +33,5 @@ __all__ = ["FCNet", "WNLinear", "TCNet", "BCNet", "BiAttention", "TriAttention",
            "StackedAttentionModel", "MCStackedAttentionModel", "build_san", "build_mc_san",
            "compute_score_with_logits", "compute_score_mc", "ScoreMeter", "evaluate", "evaluate_mc",
            "Predictions", "PredictionBuffer", "predict", "TypeMeter", "tdiuc_summary", "tdiuc_tables",
-           "Trainer", "MCTrainer", "PackedDataset", "pack_dataset", "DeviceDataset", "DeviceLoader"]
+           "Trainer", "MCTrainer", "PackedDataset", "pack_dataset", "DeviceDataset", "DeviceLoader", "bucket_plan", "bucket_widths_for",
+           "rank_plan"]

@@ -10,7 +10,8 @@ has `DataLoader(dataset, batch_size, collate_fn=utils.trim_collate)`.
 
 `pad_to=None` reproduces trim_collate (the batch's largest object count, which the host has to know: the index vector is needed there too);
 `pad_to='max'` or an int pads every batch alike, which keeps ONE captured training graph valid for a whole epoch of adaptive features (the mode-3
-product skips the row tiles of the padding objects, csrc/cti_mode3_plan.hip)."""
+product skips the row tiles of the padding objects, csrc/cti_mode3_plan.hip); `pad_to='bucket'` groups the entries of an epoch by object count
+(`bucket_plan`) so that every batch has one of a few widths, each of which a Trainer(max_graphs=K) captures once."""
 import numpy as np
 import torch
 
@@ -288,6 +289,73 @@ def epoch_order(N, shuffle=False, generator=None, rank=0, world=1):
     return perm[rank::world].contiguous()
 
 
+def bucket_widths_for(counts, K):
+    """K quantile widths of a table of object counts: the unique values of sorted(counts)[ceil((j + 1) * N / K) - 1], j = 0 .. K - 1, ascending.  The
+    last one is counts.max(); fewer than K come back when the counts have fewer distinct values at those ranks."""
+    K = int(K)
+    if K < 1:
+        raise ValueError("bucket_widths_for: K is %d" % K)
+    c = np.sort(_np(counts).reshape(-1))
+    N = c.size
+    if N == 0:
+        raise ValueError("bucket_widths_for: no counts")
+    return tuple(int(w) for w in np.unique(c[[-(-(j + 1) * N // K) - 1 for j in range(K)]]))
+
+
+def _widths(widths):
+    w = np.asarray(list(widths), np.int64).reshape(-1)
+    if w.size == 0 or w[0] < 0 or (np.diff(w) <= 0).any():
+        raise ValueError("bucket widths must be strictly ascending and not negative, got %s" % (w.tolist(),))
+    return w
+
+
+def bucket_plan(order, counts, widths, batch_size, world=1, drop_last=False):
+    """One epoch of batches grouped by object count, on the host, O(N).  `order` (int64) is the epoch's global entry order, `counts[e]` the object
+    count of entry e, `widths` strictly ascending with widths[-1] >= counts.max().  With SB = batch_size * world:
+
+      an entry's bucket is the smallest j with counts[e] <= widths[j];
+      the buckets are walked in ascending order; the pool is the carry followed by the bucket's entries in the order they have in `order`; full
+      groups of SB are cut from its front, each a batch of width widths[j]; the rest is the carry into the next bucket;
+      after the last bucket a carry that is left is the one short group, as wide as its largest count asks for (dropped with drop_last).
+
+    Returns (entries, batches): `entries` an int64 tensor, the epoch's entries group after group; `batches` a list of (lo, hi, width) over it.  Rank
+    r of `world` takes entries[lo:hi][r::world] of every group (`rank_plan`), so all ranks see the same widths in the same order, which the one
+    all-reduce per update needs.  With a single width this is order[r::world] cut by batch_size: the unbucketed loader."""
+    batch_size, world = int(batch_size), int(world)
+    if batch_size < 1 or world < 1:
+        raise ValueError("bucket_plan: batch_size %d, world %d" % (batch_size, world))
+    w = _widths(widths)
+    order = _np(order).astype(np.int64).reshape(-1)
+    c = _np(counts).reshape(-1)[order]
+    if c.size and int(c.max()) > int(w[-1]):
+        raise ValueError("bucket_plan: the last width %d is below the largest object count %d" % (int(w[-1]), int(c.max())))
+    bucket = np.searchsorted(w, c, side="left")
+    # the carry of a bucket goes in front of the next one, so the walk is a stable sort by bucket cut into groups of SB; a group cut at bucket j
+    # holds at least one entry of j and none above it (the carry is shorter than SB), so its last entry names its width
+    by_bucket = np.argsort(bucket, kind="stable")
+    entries, bucket = order[by_bucket], bucket[by_bucket]
+    SB = batch_size * world
+    full = entries.size // SB
+    end = full * SB if drop_last else entries.size
+    batches = [(lo, min(lo + SB, end), int(w[bucket[min(lo + SB, end) - 1]])) for lo in range(0, end, SB)]
+    return torch.from_numpy(np.ascontiguousarray(entries[:end])), batches
+
+
+def rank_plan(entries, batches, rank=0, world=1):
+    """What rank r of `world` visits of a bucket_plan: (its entries, its (lo, hi, width) list over them): every world-th entry of each group from r
+    on.  A short group with no entry for this rank gives it no batch."""
+    if not 0 <= rank < world:
+        raise ValueError("rank %d of world %d" % (rank, world))
+    mine, cuts, at = [], [], 0
+    for lo, hi, width in batches:
+        part = entries[lo:hi][rank::world]
+        if len(part):
+            mine.append(part)
+            cuts.append((at, at + len(part), width))
+            at += len(part)
+    return (torch.cat(mine) if mine else entries[:0]).contiguous(), cuts
+
+
 class DeviceLoader:
     """Stands where the reference builds `DataLoader(dataset, batch_size, shuffle=..., collate_fn=utils.trim_collate)`: iterable, with `len()` and
     `.dataset` (the ORIGINAL data set object: `len(loader.dataset)`, `num_ans_candidates`, `label2ans`), so `evaluate`, `predict` and the reference's
@@ -297,10 +365,19 @@ class DeviceLoader:
     takes perm[r::world]: give every rank a generator in the same state), so with `pad_to` set there is no per-batch host-to-device copy and no per-batch synchronisation.  With `pad_to=None` the
     host looks up each batch's largest object count (no copy, no synchronisation either, but every batch has its own shape).
 
+    `pad_to='bucket', bucket_widths=<ascending widths | K>` (K: `bucket_widths_for(counts, K)`, the K quantile widths of the table): once per epoch the
+    same randperm is drawn, `bucket_plan` groups it by object count, and the reordered vector is uploaded once; every batch is a slice of it padded to
+    its bucket's width, so a `Trainer(max_graphs=len(loader.widths))` replays one captured graph per width and no kernel walks the rows between a
+    small image and the table's largest.  When shuffling, the full batches are visited in a second randperm's order (the widths interleave); the one
+    short batch stays last.  Unshuffled: widths ascending, entries ascending within a bucket.  `loader.widths` are the resolved widths,
+    `loader.plan_widths` the width of each batch of the last epoch started, `loader.plan_entries` that epoch's entry numbers in visiting order (host).
+    Rank r takes every world-th entry of each GROUP of batch_size * world, so all ranks see the same widths in the same order; with drop_last the
+    short group is dropped whole.
+
     The ORDER of a shuffled epoch is not that of torch's RandomSampler for the same seed: only the guarantees are the same (every entry once per
     epoch, a new order every epoch, reproducible from the generator's state)."""
 
-    def __init__(self, ds, batch_size, shuffle=False, drop_last=False, pad_to=None, generator=None, rank=0, world=1):
+    def __init__(self, ds, batch_size, shuffle=False, drop_last=False, pad_to=None, generator=None, rank=0, world=1, bucket_widths=None):
         if batch_size < 1:
             raise ValueError("batch_size is %d" % batch_size)
         if not 0 <= rank < world:
@@ -309,14 +386,55 @@ class DeviceLoader:
         self.generator, self.rank, self.world = generator, int(rank), int(world)
         self.dataset = ds.packed.dataset
         self.local = len(range(self.rank, len(ds), self.world))          # entries this rank visits per epoch
+        self.bucketed = isinstance(pad_to, str) and pad_to == "bucket"
+        self.widths, self.plan_widths, self.plan_entries = None, None, None
+        if self.bucketed:
+            if bucket_widths is None:
+                raise ValueError("pad_to='bucket' needs bucket_widths: ascending widths, or the number of quantile widths to take from the table")
+            if isinstance(bucket_widths, (int, np.integer)):
+                bucket_widths = bucket_widths_for(ds.counts_host, bucket_widths)
+            self.widths = tuple(int(w) for w in _widths(bucket_widths))
+            if self.widths[-1] < ds.v_max:
+                raise ValueError("bucket_widths end at %d, below the %d objects of the largest image (after the cut to max_boxes=%d)"
+                                 % (self.widths[-1], ds.v_max, ds.max_boxes))
+        elif bucket_widths is not None:
+            raise ValueError("bucket_widths belongs to pad_to='bucket', pad_to is %r" % (pad_to,))
 
     def __len__(self):
+        if self.bucketed:                                    # full groups of batch_size * world, then this rank's share of the short one
+            m, t = divmod(len(self.ds), self.batch_size * self.world)
+            return m if self.drop_last else m + (t > self.rank)
         return self.local // self.batch_size if self.drop_last else (self.local + self.batch_size - 1) // self.batch_size
 
     def epoch_order(self):
         return epoch_order(len(self.ds), self.shuffle, self.generator, self.rank, self.world)
 
+    def bucket_epoch(self):
+        """This rank's plan of one bucketed epoch, on the host: (entries in visiting order, [(lo, hi, width)] over them).  Draws from the generator
+        what one epoch draws."""
+        N = len(self.ds)
+        order = epoch_order(N, self.shuffle, self.generator)
+        entries, batches = bucket_plan(order, self.ds.counts_host, self.widths, self.batch_size, self.world, self.drop_last)
+        SB = self.batch_size * self.world
+        full = [g for g in batches if g[1] - g[0] == SB]
+        if self.shuffle and full:
+            full = [full[k] for k in torch.randperm(len(full), generator=self.generator).tolist()]
+        batches = full + batches[len(full):]
+        entries = torch.cat([entries[lo:hi] for lo, hi, _ in batches]) if batches else entries
+        at, cuts = 0, []
+        for lo, hi, width in batches:
+            cuts.append((at, at + hi - lo, width))
+            at += hi - lo
+        return rank_plan(entries, cuts, self.rank, self.world)
+
     def __iter__(self):
+        if self.bucketed:
+            host, cuts = self.bucket_epoch()
+            self.plan_entries, self.plan_widths = host, [width for _, _, width in cuts]
+            dev = host.to(self.ds.device)
+            for lo, hi, width in cuts:
+                yield self.ds._assemble(dev[lo:hi], width)
+            return
         host = self.epoch_order()
         dev = host.to(self.ds.device)
         bs = self.batch_size

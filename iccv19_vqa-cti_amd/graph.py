@@ -29,13 +29,16 @@ from . import ops
 
 
 class GraphedTrainStep:
-    def __init__(self, model, optimizer, loss_fn, example_inputs, example_target, warmup=2, split_collective=None, accumulate=False):
+    def __init__(self, model, optimizer, loss_fn, example_inputs, example_target, warmup=2, split_collective=None, accumulate=False,
+                 update_graph=None):
         """loss_fn(model_output, target) -> scalar tensor.  example_inputs: tuple of tensors (shapes / dtypes are frozen); warmup eager steps run on
         a side stream first (allocator, one-time attributes, weight-norm caches), as torch's capture rules ask.  The warm-up steps DO update the
         parameters.  split_collective: None = the two-graph form exactly when the optimizer issues a collective; True / False force it.
         accumulate=True: graphs M and U of the module docstring; a warm-up step is then one micro-batch + one update and needs an optimiser with
         nothing buffered, while warmup=0 captures in whatever state the optimiser is (capturing executes nothing and leaves the buffered count alone;
-        the caller has run the step eagerly before)."""
+        the caller has run the step eagerly before).
+        update_graph (accumulate=True only): the `graph_update` of another GraphedTrainStep on the SAME optimiser, replayed instead of capturing
+        one here.  Graph U touches nothing but the optimiser's flat buffers and counters, so one serves every batch shape."""
         self.model, self.opt, self.loss_fn = model, optimizer, loss_fn
         self.accumulate = bool(accumulate)
         if self.accumulate:
@@ -44,6 +47,8 @@ class GraphedTrainStep:
                                    % (warmup, optimizer.micro_count))
             self.split = True
         else:
+            if update_graph is not None:
+                raise ValueError("update_graph belongs to GraphedTrainStep(accumulate=True)")
             if optimizer.update_freq != 1:
                 raise ValueError("GraphedTrainStep captures one update per replay: an optimiser with update_freq=%d would divide a single micro-batch by %d; "
                                  "use accumulate=True" % (optimizer.update_freq, optimizer.update_freq))
@@ -53,7 +58,7 @@ class GraphedTrainStep:
         self.static_in = tuple(t.clone() for t in example_inputs)
         self.static_tgt = example_target.clone()
         self.graph = torch.cuda.CUDAGraph()
-        self.graph_update = torch.cuda.CUDAGraph() if self.split else None
+        self.graph_update = (update_graph if update_graph is not None else torch.cuda.CUDAGraph()) if self.split else None
         # The warm-up steps run on ONE side stream, the capture on ANOTHER: with a process group the warm-up issues eager RCCL all-reduces whose
         # completion events live on the stream they ran on, and the process group's watchdog thread may still poll such an event after the
         # capture has begun -- HIP refuses a query of an event whose stream is capturing (hipErrorCapturedEvent) and the watchdog takes the
@@ -72,8 +77,9 @@ class GraphedTrainStep:
                 mode = "thread_local" if optimizer.needs_collective() else "global"
                 with torch.cuda.graph(self.graph, stream=s, capture_error_mode=mode):
                     self.static_loss = self._forward_backward()
-                with torch.cuda.graph(self.graph_update, stream=s, capture_error_mode=mode):
-                    self.opt.apply_accumulated()
+                if update_graph is None:
+                    with torch.cuda.graph(self.graph_update, stream=s, capture_error_mode=mode):
+                        self.opt.apply_accumulated()
                 optimizer.micro_count, optimizer.step_count = host   # capturing executed nothing: the host mirrors go back
                 # the modules' derived caches now point at tensors of the graph's pool that no replay has filled yet, and a buffering replay does
                 # not end in a bump of the epoch: an eager micro-step (another batch shape) must not pick them up

@@ -13,6 +13,8 @@ launch (FlatAdamaxDP.accumulate), the count of buffered micro-batches lives on t
 and batch_score come back as 0-dim device tensors -- and after `graph_after` eager calls with one sample shape the micro-step and the update are
 captured as two hipGraphs (GraphedTrainStep(accumulate=True)) and replayed from then on.  A sample of any other shape (the short last batch of an
 epoch) runs eagerly through the same accumulate() / update(), so the device-side count stays coherent.  The call that captures synchronises once.
+`max_graphs=K` keeps up to K captured micro-steps, one per sample shape (the widths of DeviceLoader(pad_to='bucket')), each with its own static
+inputs, all sharing the one captured update: an update may fold replayed micro-batches of several widths and eager ones together.
 
 `trainer.meter` is a ScoreMeter that receives, on updating steps only, what the reference's loop adds up there (train.py:83-86): the returned loss,
 the returned batch score and grad_norm; one `meter.result()` per epoch gives the numbers of the log line of train.py:94-95,104.
@@ -32,7 +34,7 @@ from .score import ScoreMeter, compute_score_with_logits, compute_score_mc   # n
 class Trainer(object):
     """FFOE: sample = [v, b, q, a, ans, t_logits]; dispatch on args.model as src/FFOE/trainer.py:166-192."""
 
-    def __init__(self, args, model, criterion, optimizer=None, *, graph_after=2):
+    def __init__(self, args, model, criterion, optimizer=None, *, graph_after=2, max_graphs=1):
         self.args = args
         dev = torch.device(args.device)
         if dev.type != "cuda" or not torch.cuda.is_available():
@@ -49,9 +51,13 @@ class Trainer(object):
         self._optimizer = optimizer
         self.meter = ScoreMeter(dev)                             # before any capture: the block must not be born in a graph's pool
         self.graph_after = graph_after
-        self.captures = 0
-        self._gs, self._gs_key, self._seen = None, None, {}
-        self._cur = self._last = self._static_last = None
+        if int(max_graphs) < 1:
+            raise ValueError("Trainer: max_graphs is %r" % (max_graphs,))
+        self.max_graphs = int(max_graphs)
+        self.captures = self.replays = 0                         # graphs captured / micro-steps replayed so far
+        self._graphs, self._seen = {}, {}                        # sample shape -> (its GraphedTrainStep, the score tensors its replay leaves)
+        self._gs = None                                          # the first capture: its graph U is the one every shape replays
+        self._cur = self._last = None
         self._steps_base = optimizer.steps_done()
 
     # ---- what the loops touch --------------------------------------------------------------------------------------------------
@@ -61,7 +67,7 @@ class Trainer(object):
 
     @property
     def graphed(self):
-        """True once the micro-step and the update have been captured (samples of the captured shape replay from then on)."""
+        """True once the micro-step of some sample shape and the update have been captured (samples of a captured shape replay from then on)."""
         return self._gs is not None
 
     def zero_grad(self):
@@ -127,14 +133,20 @@ class Trainer(object):
         self._is_tensor = [isinstance(t, torch.Tensor) for t in sample]
         tensors = tuple(t for t in sample if isinstance(t, torch.Tensor))
         key = tuple((tuple(t.shape), t.dtype) for t in tensors) + (tuple(self._is_tensor),)
-        if self._gs is None and self.graph_after is not None and self._seen.get(key, 0) >= self.graph_after:
+        if (key not in self._graphs and len(self._graphs) < self.max_graphs and self.graph_after is not None
+                and self._seen.get(key, 0) >= self.graph_after):
             # capturing executes nothing: no forward runs on this sample here, and the buffered count is left as it is
-            self._gs = GraphedTrainStep(self._model_call, self._optimizer, self._loss_call, tensors, sample[3], warmup=0, accumulate=True)
-            self._gs_key, self._static_last = key, self._last
+            gs = GraphedTrainStep(self._model_call, self._optimizer, self._loss_call, tensors, sample[3], warmup=0, accumulate=True,
+                                  update_graph=None if self._gs is None else self._gs.graph_update)
+            self._graphs[key] = (gs, self._last)
+            if self._gs is None:
+                self._gs = gs
             self.captures += 1
-        if self._gs is not None and key == self._gs_key:
-            loss = self._gs(tensors, sample[3], update_params=False)
-            self._last = self._static_last
+        if key in self._graphs:
+            gs, static_last = self._graphs[key]
+            loss = gs(tensors, sample[3], update_params=False)
+            self.replays += 1
+            self._last = static_last
         else:
             self._seen[key] = self._seen.get(key, 0) + 1
             self._optimizer.zero_grad()
