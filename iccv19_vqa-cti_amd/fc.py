@@ -7,6 +7,7 @@ weight-norm factor g/||V||_F (a scalar, computed on the device by cti_wn_scale),
 in its epilogue; the normalised weight is never materialised (the reference re-materialises it every forward
 through the weight_norm pre-forward hook)."""
 import math
+import os
 import weakref
 
 import torch
@@ -16,7 +17,7 @@ from . import ops
 from . import autograd as AG
 
 
-_NO_BATCH = __import__("os").environ.get("CTI_NO_BATCHED_SCALES", "0") == "1"      # A/B knob: every layer refreshes its own scale
+_NO_BATCH = os.environ.get("CTI_NO_BATCHED_SCALES", "0") == "1"      # A/B knob: every layer refreshes its own scale
 _scale_users = weakref.WeakSet()       # WNLinear layers that have asked for their scale: refreshed TOGETHER, in one launch pair, when stale
 
 

@@ -3,6 +3,8 @@ constructors, state_dict keys (`emb.weight`, `emb_.weight`, `rnn.weight_ih_l0`, 
 
 The lookup is one gather kernel (both tables of the 'c' mode in the same pass); the GRU runs its input projection for all time
 steps as ONE MFMA GEMM and each step as one small GEMM + a fused gate kernel; backward (BPTT) runs in HIP kernels too."""
+import os
+
 import numpy as np
 import torch
 import torch.nn as nn
@@ -10,7 +12,7 @@ import torch.nn as nn
 from . import autograd as AG
 from . import ops
 
-_ROWS16 = __import__("os").environ.get("CTI_EMB_ROWS16", "1") == "1"      # 0: fp32 word vectors + a split pass in front of the GRU's input product (rounds 1-5; A/B)
+_ROWS16 = os.environ.get("CTI_EMB_ROWS16", "1") == "1"      # 0: fp32 word vectors + a split pass in front of the GRU's input product (rounds 1-5; A/B)
 
 
 class WordEmbedding(nn.Module):

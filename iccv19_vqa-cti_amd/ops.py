@@ -1,6 +1,8 @@
 """Tensor-level wrappers over the C ABI: argument checking, output allocation (torch = device memory + stream
 plumbing only) and the launch.  Every function requires CUDA(ROCm) tensors and raises otherwise -- there is no
 CPU or eager-PyTorch path in this package."""
+import os as _os
+
 import torch
 
 from . import _lib as L
@@ -47,7 +49,7 @@ def get_precision():
 # the wrapper waits for that verdict -- it arrives while the mode-3 product is still running, so the launch pipeline does not drain -- and
 # re-runs the call in the bf16x3 mode: the caller always gets fp32-grade numbers.  'poison': no host wait (what hipGraph capture forces): an
 # out-of-range call returns NaN, never clamped numbers.
-_range_check = __import__("os").environ.get("CTI_RANGE_CHECK", "sync")      # (the environment variable: A/B of the host wait)
+_range_check = _os.environ.get("CTI_RANGE_CHECK", "sync")      # (the environment variable: A/B of the host wait)
 _range_log = {"calls": 0, "trips": 0, "last_status": 0, "consecutive": 0, "skip": 0, "last_ratio": None}
 _range_debug = False       # tests / diagnostics: also read the cancellation estimate rho of every guarded call (one more small host read) into last_ratio
 _guard_res = {}
@@ -231,9 +233,6 @@ def invalidate_caches():
     _param_epoch[0] += 1
 
 
-import os as _os
-
-
 class tuning:
     """Context manager over cti_set_tuning (tests / benchmarks only): `with ops.tuning(gemm_cfg=2, tri_chunk=64): ...` forces the plane GEMM's
     tile geometry (0 = 128x128, 1 = 256x128, 2 = 256x256) and / or the Tri softmax's chunk length, so small tensors run the instantiations that
@@ -304,7 +303,6 @@ def run_concurrently(*fns):
     if key not in _sib:
         _sib[key] = [torch.cuda.Stream(device=cur.device) for _ in fns[1:]]
     outs = [None] * len(fns)
-    capturing = torch.cuda.is_current_stream_capturing()
 
     def no_aux(f):
         _no_nested_fork[0] = True
@@ -312,18 +310,16 @@ def run_concurrently(*fns):
             return f()
         finally:
             _no_nested_fork[0] = False
+    chains = []
     for i, s in enumerate(_sib[key]):
-        s.wait_stream(cur)
-        with torch.cuda.stream(s):
+        chains.append(SideChain(s))
+        with chains[i]:
             outs[i + 1] = no_aux(fns[i + 1])
     # (round 6, re-measured: CTI_SIBLINGS_MAIN_AUX=1 lets fns[0] -- on the caller's stream, which may fork as any single model's capture does -- keep its auxiliary
     # streams: configs[3] 1 330 -> 1 448 us.  A third chain still adds contention, not overlap; default off)
     outs[0] = fns[0]() if _MAIN_AUX else no_aux(fns[0])
-    for i, s in enumerate(_sib[key]):
-        cur.wait_stream(s)
-        if not capturing:                        # (a capture's private pool keeps its blocks for the graph's lifetime)
-            for t in _tensors_of(outs[i + 1]):
-                t.record_stream(cur)             # allocated on the side stream, consumed on the caller's
+    for i, c in enumerate(chains):
+        c.join(outs[i + 1])
     return tuple(outs)
 
 
@@ -333,6 +329,40 @@ def _tensors_of(o):
     if isinstance(o, (tuple, list)):
         return [t for x in o for t in _tensors_of(x)]
     return []
+
+
+class SideChain:
+    """Work beside the current stream: ONE fork (here), any number of `with chain:` blocks, one after the other on the forking stream, whose launches go to the
+    side stream in order, ONE `join`.  side = None (no overlap: aux_stream_object's answer when it is disabled, or a CPU tensor's forward): the blocks run in
+    place and join does nothing.  Works eagerly and under hipGraph capture (fork / join become graph edges).  The model forwards' only way to another stream:
+    what a join forgets to hand over is a use-after-free, so every result of the blocks goes through `join`."""
+    __slots__ = ("side", "cur")
+
+    def __init__(self, side):
+        self.side = side
+        if side is not None:
+            self.cur = torch.cuda.current_stream()
+            side.wait_stream(self.cur)
+
+    def __enter__(self):
+        if self.side is not None:
+            torch.cuda.set_stream(self.side)
+        return self
+
+    def __exit__(self, *exc):
+        if self.side is not None:
+            torch.cuda.set_stream(self.cur)      # (what torch.cuda.stream() does, without looking the forking stream up again)
+        return False
+
+    def join(self, *results):
+        """The forking stream waits for the side stream; every tensor in `results` (nested tuples / lists, None allowed) was allocated on the side stream and is
+        consumed on the forking one from here on (a capture's private pool keeps its blocks for the graph's lifetime: nothing to record there)."""
+        if self.side is None:
+            return
+        self.cur.wait_stream(self.side)
+        if not torch.cuda.is_current_stream_capturing():
+            for t in _tensors_of(results):
+                t.record_stream(self.cur)
 
 
 # ---- optional per-kernel timing with HIP events on the launch stream (bench.py's roofline leg) -----------------

@@ -294,7 +294,7 @@ def test_glimpse_loops_agree_at_real_widths_and_the_counter_is_one_launch():
     literal loop, and the count terms must matter.  One counter launch per forward, not one per glimpse."""
     old = cti_amd.get_precision()
     cti_amd.set_precision("bf16x3")
-    bm = cti_amd.base_model
+    bm = cti_amd.pkg.glimpse_loops
     try:
         m = _real_ban(True)
         with torch.no_grad():
@@ -308,13 +308,13 @@ def test_glimpse_loops_agree_at_real_widths_and_the_counter_is_one_launch():
             r = orig(self, *a, **k)
             seen.append(r is not None)
             return r
-        bm.BanModel._forward_hoisted = spy
+        bm._ban_forward_hoisted = spy
         with torch.no_grad():
             m(v, b, q, None)
             ops.profile_start()
             hoisted, att = m(v, b, q, None)
             prof = ops.profile_stop()
-        bm.BanModel._forward_hoisted = orig
+        bm._ban_forward_hoisted = orig
         assert seen and all(seen)                                               # the hoisted loop ran (not a silent fall-through to the literal one)
         launches = [k for k in prof if k.startswith("counter_fwd")]
         assert len(launches) == 1 and len(prof[launches[0]]) == 1, prof.keys()

@@ -182,9 +182,9 @@ def test_shifted_bi_pool_vs_float64(B, V, Q, D):
 
 
 def test_hoisted_glimpse_loops_equal_the_literal_loops():
-    """base_model's hoisted glimpse loops (q / a projections of the initial sequences in one batched GEMM, the residual's projection added in the pool)
+    """glimpse_loops' hoisted glimpse loops (q / a projections of the initial sequences in one batched GEMM, the residual's projection added in the pool)
     against the literal loops of src/FFOE/base_model.py:53-64,129-134 -- same module, knob off -- and against the float64 oracle."""
-    bm = cti_amd.base_model
+    bm = cti_amd.pkg.glimpse_loops
     torch.manual_seed(34)
     cti = cti_amd.build_cti(_args(3), _ds(50, 48, 11)).to(DEV).eval()
     ban = cti_amd.build_ban(_args(4), _ds(50, 48, 11)).to(DEV).eval()
@@ -225,7 +225,7 @@ def test_unrolled_ban_loop_at_full_widths_on_every_row(prec, tol):
     """The unrolled glimpse loop of BanModel (8 glimpses, 1 024 wide, B = 256: up to 30 split-K slabs summed inside a pool) against the hoisted loop it replaces and
     the literal loop of src/FFOE/base_model.py:53-61, every row of the logits; the weight-only products C[g][j] follow a parameter change (cache key)."""
     import types
-    bm = cti_amd.base_model
+    bm = cti_amd.pkg.glimpse_loops
     old = cti_amd.get_precision()
     cti_amd.set_precision(prec)
     try:
@@ -264,11 +264,11 @@ def test_unrolled_ban_loop_at_full_widths_on_every_row(prec, tol):
 @pytest.mark.parametrize("prec,tol", [("bf16x3", 3e-5), ("bf16", 6e-3), ("f16f6", 3e-5)])
 @pytest.mark.parametrize("glimpse", [2, 3])
 def test_unrolled_tri_loop_at_full_widths_on_every_row(prec, tol, glimpse):
-    """The unrolled glimpse loop of the CTI models (base_model._tri_loop_unrolled: ONE product between two pools, the accumulated residuals in one K-concatenated
+    """The unrolled glimpse loop of the CTI models (glimpse_loops._tri_loop_unrolled: ONE product between two pools, the accumulated residuals in one K-concatenated
     product behind the last pool) against the hoisted loop it replaces and the literal loop of src/MC/base_model.py:145-150, at the Visual7W shapes of
     BASELINE configs[2] (B = 256 rows = 64 images x 4 candidates, 1 024 wide), every row of the logits; a parameter update rebuilds the weight-only products."""
     import types
-    bm = cti_amd.base_model
+    bm = cti_amd.pkg.glimpse_loops
     old = cti_amd.get_precision()
     cti_amd.set_precision(prec)
     try:

@@ -1,4 +1,4 @@
-"""The two entry points the unrolled glimpse loops of round 5 stand on (base_model._ban_forward_unrolled / _tri_loop_unrolled; reference loops
+"""The two entry points the unrolled glimpse loops of round 5 stand on (glimpse_loops._ban_forward_unrolled / _tri_loop_unrolled; reference loops
 src/FFOE/base_model.py:53-64, 129-134), each against float64 on its own:
   cti_bi_pool_shift_multi_fwd -- the shifted bi pool (src/bc.py:70-78 with q_net's ReLU formed on load) whose shift is a SUM of up to 32 addends, each a (B, ld)
                                  fp32 block or one row broadcast over the batch: the raw split-K slabs of the product that feeds it;
