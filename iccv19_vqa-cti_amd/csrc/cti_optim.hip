@@ -157,7 +157,8 @@ __global__ __launch_bounds__(256) void adamax_kernel(float* __restrict__ p, cons
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
         const float gg = g[i] * coef;
         const float mm = fmaf(b1, m[i], (1.f - b1) * gg);
-        const float uu = fmaxf(b2 * u[i], fabsf(gg) + eps);
+        const float bu = b2 * u[i], ag = fabsf(gg) + eps;
+        const float uu = (bu != bu || ag != ag) ? bu + ag : fmaxf(bu, ag);   // NaN stays NaN, like torch's amax (fmaxf alone drops it)
         m[i] = mm; u[i] = uu;
         p[i] -= lr_t * mm / uu;
     }

@@ -583,7 +583,8 @@ int cti_flat_scale_sumsq_g(float* grad, int64_t n, int world, const int64_t* mic
 int cti_counter_set(int64_t* counter, int64_t value, void* stream);
 /* norm = sqrt(sum partial); coef = min(1, max_norm / (norm + 1e-6)) (max_norm <= 0: no clipping); g' = coef * grad;
  * exp_avg = b1*exp_avg + (1-b1)*g'; exp_inf = max(b2*exp_inf, |g'| + eps); param -= lr / (1 - b1^step) * exp_avg / exp_inf.
- * grad_norm_out: NULL or one float (the pre-clip norm, for logging without a blocking .item() in the step). */
+ * The max keeps a NaN of either operand (torch.optim.Adamax takes an amax), so a NaN gradient entry leaves NaN in exp_avg, exp_inf and param.
+ * An inf norm gives coef = 0, a NaN norm coef = 1.  grad_norm_out: NULL or one float (the pre-clip norm, for logging without a blocking .item() in the step). */
 int cti_adamax_step(float* param, const float* grad, float* exp_avg, float* exp_inf, int64_t n, const float* partial, float max_norm,
                     float lr, float beta1, float beta2, float eps, int step, float* grad_norm_out, void* stream);
 size_t cti_optim_workspace_bytes(void);
